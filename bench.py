@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: routed message->peer pairs per second per tick, % of the HBM roofline.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,11 +15,11 @@ Headline workload: SURVEY.md §8(d) C3, the configuration north_star's target is
 each subscribed to a 3x3x3 neighbourhood (27M subscriptions), 10M LocalMessages per tick, 90% from
 256 Zipf-weighted Gaussian hotspots, cube_size 16, ExceptSelf, synthetic (splitmix64).
   N = 1   the whole configuration on one GPU: every step is one full tick of the hot path on
-          HBM-resident inputs (quantise -> probe -> filter -> CSR offsets + (msg, peer) pairs), with
-          the C2 line (BASELINE.json configs[1]: 100k peers, 1M messages) nested under extra.c2.
+          HBM-resident inputs (quantise -> probe -> filter -> CSR offsets + (msg, peer) pairs); with
+          --full, the C2 line (BASELINE.json configs[1]: 100k peers, 1M messages) nested under extra.c2.
   N > 1   strong scaling: every rank ingests M/N of the tick's messages. Headline: the replicated
           table (every GPU holds the whole ~10 GB table and routes its slice with the single-GPU
-          tick, no exchange; DESIGN.md §6 says why); beside it, extra.cube_hash: the cube-hash
+          tick, no exchange; DESIGN.md §6 says why); with --full, beside it, extra.cube_hash: the cube-hash
           sharded tick over RCCL (20-byte slots to the owners, row references + cube-list pools
           back; wq_sharded_route_tick_device), and under it pairs_on_owner: the owner form
           (wq_sharded_route_owner_slots_async: slots to the owners, the pairs left there). --shard
@@ -28,6 +28,14 @@ The table is built once before timing. Every timed loop is checked afterwards th
 routers' sticky health words (wq_route_health): no tick may have given up or overflowed.
 Other configs: --config c1 | c2 | c4 | c5 (bench_configs.py); --config c2 --shard cube = one world
 of N x the C2 volume over the same sharded tick (weak scaling).
+
+A run without --full sets up, warms up, times the K ticks and prints the line. --full adds everything
+that takes runs of its own: the CPU baselines (cpu_baseline*), the event-bracketed per-kernel pass
+(roofline.kernel_event_us, kernel_phases_us), the shader clock probe (clocks), C3's csr_only
+sub-line, the nested C2 line (extra.c2) and, at N > 1, the second multi-GPU form (extra.*);
+--no-extra and --no-cpu-baseline then leave parts of that out again.
+--dump-outputs DIR writes what the last timed tick returned to its caller as DIR/<name>.npy
+(float64; N > 1: DIR/rank<r>/): see dump_outputs.
 """
 from __future__ import annotations
 
@@ -51,9 +59,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (ranks) of the run; default WORLD_SIZE under a launcher, else 1")
     ap.add_argument("--config", choices=["c1", "c2", "c3", "c4", "c5"], default=None,
-                    help="default: the headline, C3 (north_star's 1M peers / 10M messages per tick) with the C2 "
-                         "line nested under extra.c2 at N = 1; c1..c5 = one SURVEY.md §8(d) config alone")
-    ap.add_argument("--no-extra", action="store_true", help="headline only (skip the nested C2 line)")
+                    help="default: the headline, C3 (north_star's 1M peers / 10M messages per tick), with --full "
+                         "the C2 line nested under extra.c2 at N = 1; c1..c5 = one SURVEY.md §8(d) config alone")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: CPU baselines, per-kernel event pass, clock "
+                         "probe, csr_only, the nested C2 line, the second multi-GPU form (see module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed ticks, write the last tick's outputs as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the nested C2 line / second form")
     ap.add_argument("--c2-world", type=int, default=0, help="C2 in this world id (>= 1023: the wide-key path)")
     ap.add_argument("--c2-shift", type=float, default=0.0,
                     help="C2 translated by this much on every axis (e.g. 2.5e7: Minecraft-scale coordinates)")
@@ -62,7 +75,7 @@ def parse():
                     help="untimed ticks (default c1/c2 200, c3 20: ~12-30 ms, so the clocks have ramped; c4/c5 2)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink C2 (tests only; 1.0 = the headline)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bound on the CPU baseline's routing work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--shard", choices=["world", "cube", "replicate", "owner"], default="world",
                     help="multi-GPU partitioning (see module docstring); C3: replicate (the default at N > 1), "
                          "cube (pairs returned to the ingesting GPU) or owner (pairs left on the owning GPU) as "
@@ -70,6 +83,8 @@ def parse():
     ap.add_argument("--pmc-file", default=os.path.join(ROOT, "profiles", "r02_pmc_route.json"),
                     help="rocprofv3 --pmc summary of the C2 tick (roofline.traffic)")
     a = ap.parse_args()
+    if a.dump_outputs and a.shard == "owner":
+        ap.error("--dump-outputs: the owner form leaves its pairs on the owning GPU, the caller receives none")
     a.headline = a.config is None
     if a.headline:
         a.config = "c3"
@@ -129,6 +144,48 @@ def roofline(B: int, tick_s: float, kernel: str, traffic=None, event_us=None) ->
     if event_us is not None:
         out["kernel_event_us"] = event_us
     return out
+
+
+DUMP_ROWS = 50_000  # messages sampled by --dump-outputs
+DUMP_MAX_PAIRS = 3_000_000  # bound on their pairs: 8 B x (3 x rows + 2 x pairs + 4) stays under 64 MB
+
+
+def dump_outputs(a, rank: int, world_size: int, offs, peers, msgs, M: int) -> None:
+    """--dump-outputs DIR: what the last timed tick handed its caller (CSR offsets[M + 1], peers[P],
+    msgs[P] or None; device tensors), as float64 .npy files (every value is a u32, exact in f64):
+      totals.npy   [P, sum of offsets, sum of peers[:P], sum of msgs[:P]] over the WHOLE output
+      rows.npy     the messages sampled: all M when M <= DUMP_ROWS, else DUMP_ROWS of them drawn by a
+                   fixed seed (ascending), cut to the leading rows that hold DUMP_MAX_PAIRS pairs
+      offsets.npy  [rows, 2]: offsets[m], offsets[m + 1] of every sampled message m
+      peers.npy    the sampled messages' slices peers[offsets[m] .. offsets[m + 1]), concatenated
+      msgs.npy     the same slices of msgs (absent when the tick writes no message index)
+    Inputs are seeded, so two builds given the same arguments write comparable files."""
+    if not a.dump_outputs:
+        return
+    import torch
+    d = a.dump_outputs if world_size == 1 else os.path.join(a.dump_outputs, f"rank{rank}")
+    os.makedirs(d, exist_ok=True)
+    if offs.is_cuda:
+        torch.cuda.synchronize(offs.device)
+    u32 =lambda t: t.to(torch.int64) & 0xFFFFFFFF  # noqa: E731  (the tensors carry u32 in int32)
+    o = u32(offs[:M + 1])
+    P = int(o[M])
+    rows = np.arange(M) if M <= DUMP_ROWS else np.sort(np.random.default_rng(0x5EED).choice(M, DUMP_ROWS, False))
+    rows = torch.from_numpy(rows.astype(np.int64)).to(offs.device)
+    lo, n = o[rows], o[rows + 1] - o[rows]
+    keep = int((torch.cumsum(n, 0) <= DUMP_MAX_PAIRS).sum())
+    rows, lo, n = rows[:keep], lo[:keep], n[:keep]
+    total = int(n.sum())
+    # pair j of the sample sits at lo[its row] + (j - first sampled pair of that row)
+    idx = torch.repeat_interleave(lo - (torch.cumsum(n, 0) - n), n) + torch.arange(total, device=offs.device)
+    totals = [P, int(o.sum()), int(u32(peers[:P]).sum())] + ([int(u32(msgs[:P]).sum())] if msgs is not None else [])
+    save = lambda name, t: np.save(os.path.join(d, name + ".npy"), np.asarray(t, dtype=np.float64))  # noqa: E731
+    save("totals", totals)
+    save("rows", rows.cpu().numpy())
+    save("offsets", torch.stack([lo, lo + n], 1).cpu().numpy())
+    save("peers", u32(peers[idx]).cpu().numpy())
+    if msgs is not None:
+        save("msgs", u32(msgs[idx]).cpu().numpy())
 
 
 def shard_workload(rank: int, scale: float = 1.0, world: int = 0, shift: float = 0.0):
@@ -335,11 +392,11 @@ def main():
         out = run_cube(a, rank, world_size, local_rank, dev)
     else:
         out = run_c2(a, rank, world_size, local_rank, dev)
-    if a.headline and world_size == 1 and not a.no_extra:
+    if a.full and a.headline and world_size == 1 and not a.no_extra:
         # the C2 line (BASELINE.json configs[1]) beside the C3 headline, with its own steps
         import copy
         a2 = copy.copy(a)
-        a2.config, a2.steps, a2.warmup, a2.headline = "c2", None, None, False
+        a2.config, a2.steps, a2.warmup, a2.headline, a2.dump_outputs = "c2", None, None, False, None
         _default_steps(a2)
         out["extra"] = {"c2": run_c2(a2, rank, world_size, local_rank, dev)}
     if rank == 0:
@@ -398,15 +455,18 @@ def run_c2(a, rank, world_size, local_rank, dev) -> dict:
 
     t_ms = timed_ticks(tick, a.steps, stream, dev, world_size, [r])
     t_max_ms, pairs_all = reduce_over_ranks(t_ms, P, dev, world_size)
+    dump_outputs(a, rank, world_size, offs, peers, msgs, M)
 
-    # kernel-only time of the route launch: HIP events recorded on the launch stream around
-    # every route kernel (wq_profile_enable), separate pass so the headline loop is untouched
-    r.profile_enable(True)
-    for _ in range(a.steps):
-        tick()
-    k_ms, launches = r.profile_read()
-    r.profile_enable(False)
-    k_avg_s = k_ms / launches / 1e3
+    k_avg_us = None
+    if a.full:
+        # kernel-only time of the route launch: HIP events recorded on the launch stream around
+        # every route kernel (wq_profile_enable), separate pass so the headline loop is untouched
+        r.profile_enable(True)
+        for _ in range(a.steps):
+            tick()
+        k_ms, launches = r.profile_read()
+        r.profile_enable(False)
+        k_avg_us = k_ms / launches * 1e3
     B = algorithmic_bytes(M, F, P)
     traffic = None
     if os.path.exists(a.pmc_file):
@@ -438,9 +498,9 @@ def run_c2(a, rank, world_size, local_rank, dev) -> dict:
             "parallelism": f"world-sharded x{world_size}", "table_build_s": round(build_s, 3),
         },
         "roofline": roofline(B, t_max_ms / a.steps / 1e3, "route tick (single launch: tick_kernel)", traffic,
-                             k_avg_s * 1e6),
+                             k_avg_us),
     }
-    if rank == 0 and world_size == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world_size == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w, a.cpu_seconds)
         threads = min(16, os.cpu_count() or 1)
         if threads > 1:
@@ -488,6 +548,7 @@ def run_cube(a, rank, world_size, local_rank, dev):
         tick()
     t_ms = timed_ticks(tick, a.steps, stream, dev, world_size, [r])
     t_max_ms, pairs_all = reduce_over_ranks(t_ms, state["P"], dev, world_size)
+    dump_outputs(a, rank, world_size, offs, peers, msgs, M)
     out = {
         "metric": METRIC,
         "value": pairs_all * a.steps / (t_max_ms / 1e3),
@@ -513,7 +574,7 @@ def run_cube(a, rank, world_size, local_rank, dev):
                              t_max_ms / a.steps / 1e3, "whole sharded tick per GPU (shard + exchanges + owner route "
                              "+ unshard)"),
     }
-    if rank == 0 and world_size == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world_size == 1 and not a.no_cpu_baseline:
         w1 = shard_workload(0, a.scale)
         out["cpu_baseline"] = cpu_baseline(w1, a.cpu_seconds)
     r.close()

@@ -148,21 +148,24 @@ def run_c1(a, rank, world_size, local_rank, dev):
     assert c["overflow"] == 0 and c["error"] == 0, c
     t_ms = timed_ticks(lambda: r.route_device(*args, 0), a.steps, stream, dev, world_size, [r])
     t_max_ms, pairs_all = reduce_over_ranks(t_ms, P, dev, world_size)
-    r.profile_enable(True)
-    for _ in range(a.steps):
-        r.route_device(*args, 0)
-    k_ms, launches = r.profile_read()
-    r.profile_enable(False)
-    k_s = k_ms / launches / 1e3
+    bench.dump_outputs(a, rank, world_size, offs, peers, None, M)
+    k_us = None
+    if a.full:  # kernel-only time of the route launch, a pass of its own (wq_profile_enable)
+        r.profile_enable(True)
+        for _ in range(a.steps):
+            r.route_device(*args, 0)
+        k_ms, launches = r.profile_read()
+        r.profile_enable(False)
+        k_us = k_ms / launches * 1e3
     B = algorithmic_bytes(M, F, P)
     out = _line(a, world_size, pairs_all * a.steps / (t_max_ms / 1e3), t_max_ms / a.steps, "weak",
                 "C1: 1 world, 1k peers x 1 cube, 10k LocalMessages/tick, U[-64,64)^3, cube_size 16, ExceptSelf "
                 "(BASELINE.json configs[0], the reference's CPU case; launch-latency bound on a GPU)",
                 {"messages_per_tick": M, "peers": w.n_peers, "pairs_per_tick": P, "candidates_per_tick": F,
                  "parallelism": f"replicas x{world_size}"},
-                roofline(B, t_max_ms / a.steps / 1e3, "route tick (single launch)", None, k_s * 1e6),
+                roofline(B, t_max_ms / a.steps / 1e3, "route tick (single launch)", None, k_us),
                 "synthetic (splitmix64, SURVEY.md §8(d) C1 generator)")
-    if rank == 0 and world_size == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world_size == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"], out["cpu_baseline_faithful"] = _cpu_c1(w, 20)
     r.close()
     return out
@@ -215,16 +218,7 @@ def run_c3(a, rank, world_size, local_rank, dev):
     P, F = int(c["n_pairs"]), int(c["n_candidates"])
     assert c["overflow"] == 0 and c["error"] == 0, c
     t_ms = timed_ticks(lambda: r.route_device(*args, 0), a.steps, stream, dev, 1, [r])
-    # the GPU's shader clock right after the timed region (the box-to-box spread of the headline is
-    # partly clock: VERDICT r5 Weak #5), then one event-bracketed launch per tick with events between
-    # its kernels, so the line says which kernel moved
-    sclk_mhz = r.probe_sclk()
-    r.profile_enable(True)
-    for _ in range(a.steps):
-        r.route_device(*args, 0)
-    k_ms, launches, ph_ms, n_ph = r.profile_read_phases()
-    r.profile_enable(False)
-    k_avg_s = k_ms / launches / 1e3
+    bench.dump_outputs(a, rank, 1, offs, peers, msgs, M)
     B = algorithmic_bytes(M, F, P)
     kernel = ("route tick (count / tile_scan / emit launches, wq_set_fanout_hint)" if P / M >= 16
               else "route tick (single launch: tick_kernel)")
@@ -235,8 +229,29 @@ def run_c3(a, rank, world_size, local_rank, dev):
                 {"messages_per_tick": M, "peers": w.n_peers, "subscriptions": int(st["n_entries"]),
                  "cubes": int(st["n_cubes"]), "pairs_per_tick": P, "candidates_per_tick": F,
                  "parallelism": "1 GPU", "table_build_s": round(build_s, 3), "generate_s": round(gen_s, 1)},
-                roofline(B, t_ms / a.steps / 1e3, kernel, _pmc_traffic(PMC_C3, M, P), k_avg_s * 1e6),
+                roofline(B, t_ms / a.steps / 1e3, kernel, _pmc_traffic(PMC_C3, M, P)),
                 "synthetic (splitmix64, SURVEY.md §8(d) C3 generator)")
+    out["xgmi_model"] = _xgmi_model()
+    if a.full:
+        _c3_full(a, out, r, w, args, offs, peers, stream, dev, M, P, F, B)
+    r.close()
+    return out
+
+
+def _c3_full(a, out, r, w, args, offs, peers, stream, dev, M, P, F, B):
+    """--full on the one-GPU C3 line: what takes runs of its own after the timed region."""
+    import torch
+    cap = args[8]
+    # the GPU's shader clock right after the timed region (the box-to-box spread of the headline is
+    # partly clock: VERDICT r5 Weak #5), then one event-bracketed launch per tick with events between
+    # its kernels, so the line says which kernel moved
+    sclk_mhz = r.probe_sclk()
+    r.profile_enable(True)
+    for _ in range(a.steps):
+        r.route_device(*args, 0)
+    k_ms, launches, ph_ms, n_ph = r.profile_read_phases()
+    r.profile_enable(False)
+    out["roofline"]["kernel_event_us"] = k_ms / launches * 1e3
     if n_ph:
         us = [x / n_ph * 1e3 for x in ph_ms]
         # per kernel: its own §8(d) share — count 69M (inputs + bucket record), emit 4F + 8P + 4(M+1)
@@ -265,9 +280,6 @@ def run_c3(a, rank, world_size, local_rank, dev):
         threads = min(16, os.cpu_count() or 1)
         if threads > 1:  # SURVEY.md §8(d) cpu_ref_mt: the same restatement on the host's cores
             out["cpu_baseline_mt"] = bench.cpu_baseline_mt(w, threads)
-    out["xgmi_model"] = _xgmi_model()
-    r.close()
-    return out
 
 
 XGMI_G8 = "r03_c3_xgmi_g8.json"  # tools/shard_volume.py --G 8: full C3 as 8 hub shards on one GPU
@@ -373,6 +385,7 @@ def _c3_replicated(a, w, rank, world_size, local_rank, dev, stream, sl):
     P, F = int(c["n_pairs"]), int(c["n_candidates"])
     assert c["overflow"] == 0 and c["error"] == 0, c
     t_ms = timed_ticks(lambda: r.route_device(*args, 0), a.steps, stream, dev, world_size, [r])
+    bench.dump_outputs(a, rank, world_size, offs, peers, msgs, M)
     r.close()
     (t_max_ms,) = bench.allreduce([t_ms], "max", dev, world_size)
     pairs_all, B_all = bench.allreduce([P, algorithmic_bytes(M, F, P)], "sum", dev, world_size)
@@ -416,6 +429,7 @@ def _c3_cube(a, w, rank, world_size, local_rank, dev, stream, sl, owner_form: bo
     for _ in range(max(a.warmup, 2)):
         tick()
     t_ms = timed_ticks(tick, a.steps, stream, dev, world_size, [r])
+    bench.dump_outputs(a, rank, world_size, offs, peers, msgs, M)
     c = _counters(cnt)[0]
     assert c["error"] == 0 and c["overflow"] == 0, c
     exact, budgeted = r.shard_tick_stats()
@@ -524,7 +538,8 @@ def _run_c3_multi(a, w, rank, world_size, local_rank, dev, gen_s):
     M_all = len(w.world)
     M = sl[1] - sl[0]
     res = {}
-    forms = [head] if (world_size == 1 or a.no_extra) else [head, "cube" if head == "replicate" else "replicate"]
+    second = a.full and world_size > 1 and not a.no_extra  # the other form too, under extra
+    forms = [head, "cube" if head == "replicate" else "replicate"] if second else [head]
     name = {"cube": "cube_hash", "replicate": "replicated_table", "owner": "owner_slots"}
 
     def line():
@@ -593,7 +608,8 @@ def _run_c3_multi(a, w, rank, world_size, local_rank, dev, gen_s):
             elif f == "owner":
                 res[f] = _c3_owner(a, w, rank, world_size, local_rank, dev, stream, sl)
             else:
-                res[f] = _c3_cube(a, w, rank, world_size, local_rank, dev, stream, sl, owner_form=not a.no_extra)
+                res[f] = _c3_cube(a, w, rank, world_size, local_rank, dev, stream, sl,
+                                  owner_form=a.full and not a.no_extra)
         except Exception as e:  # noqa: BLE001
             if i == 0:
                 raise
@@ -643,7 +659,8 @@ def _ops_tensor(ops, dev):
     return torch.from_numpy(raw.copy()).to(dev)
 
 
-def _churn_ticks(a, r, dev, stream, ticks, M, world_t, sender_t, repl_t, positions=False):
+def _churn_ticks(a, r, dev, stream, ticks, M, world_t, sender_t, repl_t, positions=False, rank=0,
+                 world_size=1):
     """Runs the pregenerated ticks (ops, pos) through update + route; returns per-phase timings."""
     import torch
     ops_d = [_ops_tensor(t[0], dev) for t in ticks]
@@ -676,6 +693,7 @@ def _churn_ticks(a, r, dev, stream, ticks, M, world_t, sender_t, repl_t, positio
     k_ms, launches = r.profile_read()
     r.profile_enable(False)
     upd1, fb = r.update_counts()
+    bench.dump_outputs(a, rank, world_size, offs, peers, msgs, M)
     c = _counters(cnt)[a.warmup:]
     assert (c["overflow"] == 0).all() and (c["error"] == 0).all()
     return {"t_ms": t_ms, "route_ms": k_ms, "launches": launches, "P": int(c["n_pairs"].sum()),
@@ -710,7 +728,7 @@ def run_c4(a, rank, world_size, local_rank, dev):
     repl_t = torch.zeros(M, dtype=torch.uint8, device=dev)
     if world_size > 1:
         dist.barrier()
-    res = _churn_ticks(a, r, dev, stream, ticks, M, world_t, sender_t, repl_t)
+    res = _churn_ticks(a, r, dev, stream, ticks, M, world_t, sender_t, repl_t, rank=rank, world_size=world_size)
     t_max_ms, pairs_all = reduce_over_ranks(res["t_ms"], res["P"], dev, world_size)
     steps = a.steps
     k_avg_s = res["route_ms"] / res["launches"] / 1e3
@@ -732,7 +750,7 @@ def run_c4(a, rank, world_size, local_rank, dev):
                  "kernel": "whole tick (incremental update + route); route launch alone below",
                  "kernel_avg_us": k_avg_s * 1e6, "algorithmic_bytes": B},
                 "synthetic (splitmix64, SURVEY.md §8(d) C4 generator)")
-    if rank == 0 and world_size == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world_size == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = _cpu_churn_sample(init, ticks, c4.world, a.cpu_seconds)
     r.close()
     return out
@@ -827,7 +845,7 @@ def run_c5(a, rank, world_size, local_rank, dev):
                  "kernel_avg_us": k_avg_s * 1e6, "algorithmic_bytes": B},
                 "synthetic (splitmix64, SURVEY.md §8(d) C5 generator)")
     r.close()
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         tick_ops = [t[0] for t in ticks[:a.warmup + 1]]
         out["cpu_baseline"] = _cpu_c5_measured(init, tick_ops, ticks[a.warmup][1], c5.radius)
         out["cpu_baseline_faithful"] = _cpu_c5_sample(init, tick_ops, ticks[a.warmup][1], c5.radius, a.cpu_seconds)
@@ -973,6 +991,7 @@ def _run_c5_sharded(a, rank, world_size, local_rank, dev):
     for _ in range(a.warmup):
         one()
     t_ms = timed_ticks(one, a.steps, stream, dev, world_size, [r])
+    bench.dump_outputs(a, rank, world_size, offs, peers, msgs, M)
     c = _counters(cnt)[a.warmup:]
     assert (c["error"] == 0).all() and (c["overflow"] == 0).all(), c
     t_max_ms, pairs_all = reduce_over_ranks(t_ms, int(c["n_pairs"].sum()), dev, world_size)

@@ -28,7 +28,7 @@ def test_bench_two_rank_rehearsal_line_matches_one_rank():
     common = ["--scale", "0.2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
     env = dict(os.environ, WQ_BENCH_ONE_GPU="1")
     env.pop("WORLD_SIZE", None)
-    two = _bench("--gpus", "2", *common, env=env)
+    two = _bench("--gpus", "2", "--full", *common, env=env)  # --full: the second form, extra.cube_hash
     one = _bench("--gpus", "1", "--no-extra", *common, env=env)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["config"]["pairs_per_tick"] == one["config"]["pairs_per_tick"] > 0
@@ -42,3 +42,23 @@ def test_bench_two_rank_rehearsal_line_matches_one_rank():
     cube = two["extra"]["cube_hash"]
     assert "error" not in cube, cube
     assert cube["value"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_its_last_tick(tmp_path):
+    """A run without --full carries the headline figures and none of the sub-lines that take runs of
+    their own; --dump-outputs writes the last timed tick's CSR sample, consistent with the line."""
+    import numpy as np
+    d = tmp_path / "dump"
+    line = _bench("--gpus", "1", "--scale", "0.02", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert not {"cpu_baseline", "cpu_baseline_mt", "csr_only", "clocks", "extra"} & set(line), sorted(line)
+    assert "kernel_event_us" not in line["roofline"]
+    L = {n: np.load(d / f"{n}.npy") for n in ("totals", "rows", "offsets", "peers", "msgs")}
+    assert all(v.dtype == np.float64 for v in L.values())
+    assert L["totals"][0] == line["config"]["pairs_per_tick"]
+    n = (L["offsets"][:, 1] - L["offsets"][:, 0]).astype(np.int64)
+    assert len(L["rows"]) == len(n) > 0 and len(L["peers"]) == len(L["msgs"]) == n.sum() > 0
+    assert (L["msgs"] == np.repeat(L["rows"], n)).all()  # every pair names its own message
+    assert L["peers"].max() < line["config"]["peers"]

@@ -8,7 +8,7 @@
 #     tests              the whole GPU suite                       (t_all)
 #     tests=FILE[,FILE]  those GPU test files                       (t_<first file>)
 #     smoke              __graft_entry__ build-free smoke           (smoke)
-#     bench              the default bench line                     (b_default)
+#     bench              the default bench line, --full             (b_default)
 #     bench=ARGS         bench.py with ARGS (commas for spaces)     (b_<args>)
 #     kstats=NAME        rocprofv3 kernel stats of the default line (tools/kstats_bench.sh)
 #     replay             tools/shard_replay.py, G = 8, shard 0      (replay)
@@ -25,7 +25,7 @@ for step in "$@"; do
     tests)   if [ -z "$val" ]; then $S t_all 1100 $PYTEST tests
              else f=${val%%,*}; f=${f##*/}; $S "t_${f%.py}" 900 $PYTEST ${val//,/ }; fi ;;
     smoke)   $S smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)   if [ -z "$val" ]; then $S b_default 400 python bench.py
+    bench)   if [ -z "$val" ]; then $S b_default 400 python bench.py --full
              else n=${val//[^a-z0-9]/_}; $S "b_${n:0:40}" 400 python bench.py ${val//,/ }; fi ;;
     kstats)  timeout -k 10 420 bash tools/kstats_bench.sh "${val:-default}" > "gpurun_out/ks_${val:-default}.log" 2>&1 ;;
     replay)  $S replay 400 python tools/shard_replay.py --G 8 --rank 0 --ticks 20 ;;
