@@ -217,6 +217,62 @@ int wq_set_peer_positions(wq_router* h, const double* pos, size_t n_peers);
 int wq_set_peer_positions_device(wq_router* h, const double* d_pos, size_t n_peers);
 int wq_set_radius(wq_router* h, double radius);
 
+/* ---- follow moving peers: the subscription deltas generated on the GPU ----
+ * An extension the reference does not have: there every client works out its own AreaSubscribe /
+ * AreaUnsubscribe messages (area_subscribe.rs / area_unsubscribe.rs), and a host driving this table
+ * would have to produce and upload one 40-byte wq_op per changed cube. Here the host hands over one
+ * world id and one position per peer and the handle derives the ops itself.
+ *   neighbourhood  of (world w, position p), cube size s, reach r: the cubes
+ *                  CubeArea::from_vector3(p + s*d) for d in {-r..r}^3 — one f64 add per axis, no
+ *                  contraction, the table's own quantiser; it can hold fewer than (2r+1)^3 cubes.
+ *   follow state   per peer id the world and position it was last followed at (28 B per peer;
+ *                  WQ_WORLD_INVALID = not followed). It is separate from the radius filter's
+ *                  positions: wq_set_peer_positions* and the filter neither read nor write it.
+ *   one call       world[n] and pos[n x 3], indexed by peer id. For every peer i < n, with O = the
+ *                  neighbourhood of its stored state (empty if not followed) and N = the one of
+ *                  (world[i], pos[i]) (empty if world[i] == WQ_WORLD_INVALID: stop following), the
+ *                  call applies UNSUBSCRIBE for every cube of O \ N and SUBSCRIBE for every cube of
+ *                  N \ O — an exact set difference, cell edges included — and then stores the new
+ *                  state. Peers >= n are untouched.
+ * The ops depend on the old and new follow state only, never on what the table holds:
+ * subscriptions made through wq_apply_ops are not touched, and wq_remove_peers does NOT clear the
+ * follow state of the peers it removes (stop following them with WQ_WORLD_INVALID, or
+ * wq_follow_reset).
+ * The op stream is deterministic, byte for byte: ascending peer id; within a peer the unsubscribes,
+ * then the subscribes; each group in lexicographic (dx, dy, dz) order over the first offset that
+ * yields each distinct cube. Ops carry key_is_raw = 0 and the offset position p + s*d — what a host
+ * handler would send — so keys without a packed form (NaN, huge coordinates, world ids >= 2^24 - 1)
+ * take the rebuild path they take through wq_apply_ops_device. Padding bytes are zero.
+ * A call counts the ops (one lane per peer), reads the totals back (its only host read), sizes the
+ * handle's op buffer exactly — WQ_E_OOM, or WQ_E_CAPACITY at more than 2^32-1 ops, is returned
+ * before any follow state changes — writes the ops and the new state, and applies the ops as
+ * wq_apply_ops_device does (incremental or rebuild, the same pending-batch protocol; the previous
+ * batch is folded in first). The _device form reads its arrays on the handle's stream and is
+ * asynchronous after the read-back: keep the arrays unchanged until the stream has passed the call;
+ * a wq_route_tick_device issued right after it sees the updated table. Multi-GPU handles generate on
+ * devices[0] and distribute the ops as wq_apply_ops_device does, in both layouts; the sharded
+ * entry points (wq_shard_*, wq_sharded_*) have no follow form. */
+typedef struct wq_follow_result {
+    uint64_t n_unsubscribe; /* ops of this call */
+    uint64_t n_subscribe;
+    uint64_t n_followed;    /* peers followed after the call (the whole handle) */
+} wq_follow_result;
+/* Reach r of the neighbourhood, 0..2 (default 1: 3x3x3). Only while no peer is followed
+ * (WQ_E_INVALID otherwise; reach > 2: WQ_E_INVALID). */
+int wq_follow_set_reach(wq_router* h, uint32_t reach);
+/* Drops all follow state; emits no op (the table keeps its subscriptions). */
+int wq_follow_reset(wq_router* h);
+/* out is nullable. A null array with n > 0: WQ_E_INVALID. */
+int wq_follow_peers(wq_router* h, const uint32_t* world, const double* pos, size_t n, wq_follow_result* out);
+int wq_follow_peers_device(wq_router* h, const uint32_t* d_world, const double* d_pos, size_t n,
+                           wq_follow_result* out);
+/* The ops of the latest follow call: a device pointer into the handle's op buffer (NULL when the
+ * call had none), valid until the next follow call on the handle. */
+int wq_follow_last_ops(wq_router* h, const wq_op** d_ops, size_t* n);
+/* The same copied to host memory (synchronous); *n = the op count, WQ_E_CAPACITY if it exceeds
+ * `capacity` (nothing copied). */
+int wq_follow_read_ops(wq_router* h, wq_op* out, size_t capacity, size_t* n);
+
 /* ---- tick shape: the caller's expected recipients per message (e.g. its previous tick's
  * n_pairs / M; no reference counterpart — the Rust loop routes one message at a time,
  * thread.rs:125-146). At >= WQ_HEAVY_FANOUT the tick runs as count / scan / emit launches, whose

@@ -217,6 +217,16 @@ struct wq_router {
     bool shard_expanded = false;    // wq_debug_set_shard_form: expanded pairs back instead of row references
     int shard_inject = 0;           // wq_debug_inject_shard_failure: fail the next sharded tick's step 1 or 3
     wq::MultiCtx* multi = nullptr;  // wq_router_create_multi: this handle drives G shard handles
+    // follow (wq_follow.hip): per peer id the world (WQ_WORLD_INVALID: not followed) and position it
+    // was last followed at — separate from the radius filter's ppos — and the scratch of a call: op
+    // counts, their exclusive prefix, the packed axis masks, the totals (device / pinned), the op
+    // buffer of the latest call (a pending batch may be re-applied from it) and the host form's staging
+    wq::DevBuf fol_world, fol_pos, fol_cnt, fol_off, fol_mask, fol_tot, fol_ops, fol_in;
+    void* fol_pinned = nullptr;
+    uint64_t fol_cap = 0;    // peers the state covers
+    uint64_t fol_n = 0;      // peers followed now
+    uint64_t fol_n_ops = 0;  // ops of the latest call
+    uint32_t fol_reach = 1;
 };
 
 namespace wq {
@@ -284,6 +294,8 @@ int table_ensure_any(wq_router* h);
 int set_error(wq_router* h, int code, const char* what, hipError_t e = hipSuccess);
 // wq_sharded.hip: frees the exchange and its workspace (destroys an RCCL communicator).
 void shard_release(wq_router* h);
+// wq_follow.hip: frees the follow state and its scratch.
+void follow_release(wq_router* h);
 // wq_multi.hip: the multi-GPU handle's side of the entry points (h->multi != nullptr)
 int multi_merge_any(wq_router* h);
 int multi_apply_ops(wq_router* h, const wq_op* ops, size_t n);

@@ -31,6 +31,11 @@ class WQError(RuntimeError):
         self.code = code
 
 
+class FollowResult(ctypes.Structure):  # struct wq_follow_result
+    _fields_ = [("n_unsubscribe", ctypes.c_uint64), ("n_subscribe", ctypes.c_uint64),
+                ("n_followed", ctypes.c_uint64)]
+
+
 def load_library(build_if_missing: bool = True):
     """Load libwq_router.so (building it with hipcc if it is absent and hipcc exists)."""
     global _lib
@@ -92,6 +97,12 @@ def load_library(build_if_missing: bool = True):
         "wq_set_peer_positions": ([vp, vp, sz], i32),
         "wq_set_peer_positions_device": ([vp, vp, sz], i32),
         "wq_set_radius": ([vp, ctypes.c_double], i32),
+        "wq_follow_set_reach": ([vp, u32], i32),
+        "wq_follow_reset": ([vp], i32),
+        "wq_follow_peers": ([vp, vp, vp, sz, ctypes.POINTER(FollowResult)], i32),
+        "wq_follow_peers_device": ([vp, vp, vp, sz, ctypes.POINTER(FollowResult)], i32),
+        "wq_follow_last_ops": ([vp, ctypes.POINTER(vp), ctypes.POINTER(sz)], i32),
+        "wq_follow_read_ops": ([vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_set_fanout_hint": ([vp, ctypes.c_double], i32),
         "wq_debug_route_shape": ([vp, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
         "wq_route_health": ([vp, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
@@ -478,6 +489,47 @@ class Router:
 
     def set_radius(self, radius: float) -> None:
         self._check(self.lib.wq_set_radius(self.h, float(radius)))
+
+    # ---- follow moving peers (include/wq_router.h; host reference: follow.py) ----
+    def follow_set_reach(self, reach: int) -> None:
+        """Reach of the followed neighbourhood, 0..2 (default 1); only while no peer is followed."""
+        self._check(self.lib.wq_follow_set_reach(self.h, reach))
+
+    def follow_reset(self) -> None:
+        """Drops all follow state; no op is emitted."""
+        self._check(self.lib.wq_follow_reset(self.h))
+
+    def follow_peers(self, world, pos) -> dict:
+        """world[n], pos[n x 3] indexed by peer id (abi.WORLD_INVALID: stop following): the table
+        follows the moves. Returns {n_unsubscribe, n_subscribe, n_followed}."""
+        w = np.ascontiguousarray(world, dtype=np.uint32)
+        p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        if len(p) != len(w):
+            raise ValueError("world and pos must cover the same peers")
+        res = FollowResult()
+        self._check(self.lib.wq_follow_peers(self.h, _p(w), _p(p), len(w), ctypes.byref(res)))
+        return {f: getattr(res, f) for f, _ in FollowResult._fields_}
+
+    def follow_peers_device(self, world_ptr: int, pos_ptr: int, n: int) -> dict:
+        """The same on device arrays, read on the handle's stream; asynchronous after the read-back
+        of the op totals (keep the arrays unchanged until the stream has passed the call)."""
+        res = FollowResult()
+        self._check(self.lib.wq_follow_peers_device(self.h, world_ptr or None, pos_ptr or None, n, ctypes.byref(res)))
+        return {f: getattr(res, f) for f, _ in FollowResult._fields_}
+
+    def follow_last_ops_device(self):
+        """(device pointer or 0, n) of the latest follow call's ops (wq_follow_last_ops)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self.lib.wq_follow_last_ops(self.h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value or 0, n.value
+
+    def follow_last_ops(self) -> np.ndarray:
+        """The latest follow call's ops, copied to the host (abi.OP_DTYPE, stream order)."""
+        _, n = self.follow_last_ops_device()
+        out = np.zeros(n, dtype=abi.OP_DTYPE)
+        got = ctypes.c_size_t()
+        self._check(self.lib.wq_follow_read_ops(self.h, _p(out) if n else None, n, ctypes.byref(got)))
+        return out[: got.value]
 
     def set_fanout_hint(self, pairs_per_message: float) -> None:
         """Expected recipients per message (e.g. the previous tick's P / M): >= 16 selects the
