@@ -514,6 +514,73 @@ int wq_peer_major_device(wq_router* h, const uint32_t* d_offsets, const uint32_t
                          size_t n_pairs, const uint32_t* d_connected, uint32_t n_peers,
                          uint32_t* d_peer_offsets, uint32_t* d_msgs_out);
 
+/* ---- interest changes: who entered and who left each row between two ticks ----
+ * A server that replicates entities (row m of every tick = entity m) sends a spawn to the
+ * observers that entered an entity's interest set since the last tick and a despawn to those that
+ * left. An extension like follow and the radius filter: the reference stores neither positions nor
+ * earlier results (local_message.rs:52-86 routes and forgets).
+ *
+ * Inputs
+ *   - Both inputs are CSRs over the same n_rows rows: offsets[n_rows + 1] from 0, peers ascending
+ *     and distinct within a row — what wq_route_tick* and wq_route_global* write.
+ *   - Row identity across the two ticks is the caller's business: row m is the same entity in both.
+ *   - old_capacity and new_capacity are the element counts of the two peers arrays, the `capacity`
+ *     the ticks were given.
+ *   - The kernels clamp every row bound to them: row m is the part of [offsets[m], offsets[m + 1])
+ *     inside [0, capacity), empty when offsets[m + 1] < offsets[m].
+ *   - A truncated tick (one whose own `overflow` was set) can never make the diff read outside an
+ *     array. Its rows then compare only what was written, and `error` bit 0 is set.
+ *   - No input is ever dereferenced outside [0, capacity) or [0, n_rows], whatever it holds.
+ *   - Offsets that descend in several places can make the clamped rows overlap; a side's rows are
+ *     walked up to 2 x capacity elements in total (one descending pair never reaches that), the
+ *     rows past it are taken as empty.
+ * Outputs
+ *   - Row m of the entered CSR is new_m \ old_m, row m of the left CSR is old_m \ new_m, both
+ *     ascending.
+ *   - Both output offset arrays are always written in full, [n_rows + 1] from 0, even on overflow.
+ *   - Pairs at index >= capacity are not written, as wq_route_tick_device does.
+ *   - The left side is optional: with d_left_offsets == NULL, d_left_peers must also be NULL and
+ *     left_capacity 0. The left set is then neither computed nor counted: n_left = 0 and overflow
+ *     bit 1 is never set.
+ *   - d_counters is nullable.
+ *   - Output is deterministic, byte for byte: placement comes from prefix sums, never from atomic
+ *     arrival order.
+ * Execution
+ *   - wq_csr_diff_device is asynchronous on the handle's stream and reads nothing back. The grids
+ *     are sized from n_rows and the capacities; the pair totals are read on the device.
+ *   - Scratch lives in the handle, grow-only: at most 16 (n_rows + 1) + 3 (new_capacity +
+ *     old_capacity) / 4 bytes. A steady-state call does no hipMalloc, no memset and no memcpy launch.
+ *   - wq_csr_diff uploads, runs and downloads. It returns WQ_E_CAPACITY with *n_entered and
+ *     *n_left set when an output is too small; it then copies the offsets and no pairs. n_left may
+ *     be NULL when the left side is off.
+ * Limits and handle kinds
+ *   - n_rows < 2^32 - 1024 and capacities <= 2^32 - 1 (larger ones count as that), the route's
+ *     limits. n_rows == 0 is valid and writes the two offsets[0] = 0.
+ *   - WQ_E_INVALID for a null handle, a null required array with a non-zero size, or a half-given
+ *     left side; nothing is launched then.
+ *   - As wq_peer_major_device the call needs only a stream and scratch: a multi-GPU handle runs it
+ *     on the handle's own stream with the arrays on devices[0]. The sharded views have no form of
+ *     their own. */
+typedef struct wq_diff_counters {
+    uint64_t n_entered;  /* sum over rows of |new \ old| */
+    uint64_t n_left;     /* sum over rows of |old \ new| */
+    uint32_t overflow;   /* bit 0: n_entered > ent_capacity, bit 1: n_left > left_capacity */
+    uint32_t error;      /* bit 0: some row had offsets[m+1] < offsets[m] or reached past its
+                            array's capacity; such a row is taken as the part inside bounds */
+} wq_diff_counters;
+int wq_csr_diff_device(wq_router* h, size_t n_rows,
+                       const uint32_t* d_old_offsets, const uint32_t* d_old_peers, size_t old_capacity,
+                       const uint32_t* d_new_offsets, const uint32_t* d_new_peers, size_t new_capacity,
+                       uint32_t* d_ent_offsets, uint32_t* d_ent_peers, size_t ent_capacity,
+                       uint32_t* d_left_offsets, uint32_t* d_left_peers, size_t left_capacity,
+                       wq_diff_counters* d_counters);
+int wq_csr_diff(wq_router* h, size_t n_rows,
+                const uint32_t* old_offsets, const uint32_t* old_peers, size_t old_capacity,
+                const uint32_t* new_offsets, const uint32_t* new_peers, size_t new_capacity,
+                uint32_t* ent_offsets, uint32_t* ent_peers, size_t ent_capacity,
+                uint32_t* left_offsets, uint32_t* left_peers, size_t left_capacity,
+                size_t* n_entered, size_t* n_left);
+
 /* ---- health of asynchronous ticks ----
  * OR of wq_route_counters.error (error_bits) and of .overflow over every route / global call since
  * the previous wq_route_health on this handle; reading clears them (synchronises the stream). A

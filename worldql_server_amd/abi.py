@@ -39,6 +39,13 @@ OP_DTYPE = np.dtype({
 COUNTERS_DTYPE = np.dtype([("n_pairs", np.uint64), ("n_candidates", np.uint64),
                            ("overflow", np.uint32), ("error", np.uint32)])
 
+# struct wq_diff_counters: 24 bytes (wq_csr_diff_device)
+DIFF_COUNTERS_DTYPE = np.dtype([("n_entered", np.uint64), ("n_left", np.uint64),
+                                ("overflow", np.uint32), ("error", np.uint32)])
+DIFF_OVERFLOW_ENTERED = 1  # wq_diff_counters.overflow bits
+DIFF_OVERFLOW_LEFT = 2
+DIFF_ERROR_ROWS = 1        # wq_diff_counters.error bit 0: a row was cut to the part inside bounds
+
 
 def make_op(world: int, peer: int, kind: int, pos=None, key=None) -> np.void:
     """One wq_op record; give `pos` (Vector3, quantised) or `key` (raw CubeArea)."""

@@ -227,6 +227,11 @@ struct wq_router {
     uint64_t fol_n = 0;      // peers followed now
     uint64_t fol_n_ops = 0;  // ops of the latest call
     uint32_t fol_reach = 1;
+    // interest diff (wq_csr_diff.hip): per row the clamped lengths of both sides and their prefix,
+    // per granule the counts and their prefix, the granules' flag words, and two error slots (each
+    // call zeroes the next call's) followed by the host form's counters
+    wq::DevBuf diff_len, diff_pre, diff_cnt, diff_base, diff_flags, diff_err;
+    uint64_t diff_calls = 0;
 };
 
 namespace wq {
@@ -296,6 +301,14 @@ int set_error(wq_router* h, int code, const char* what, hipError_t e = hipSucces
 void shard_release(wq_router* h);
 // wq_follow.hip: frees the follow state and its scratch.
 void follow_release(wq_router* h);
+// wq_csr_diff.hip: the diff of two ticks' CSRs on device arrays (asynchronous; own: the counters
+// also go to the handle's scratch, after the two error slots of diff_err), and its scratch's release.
+int launch_csr_diff(wq_router* h, size_t n_rows, const uint32_t* d_old_offsets, const uint32_t* d_old_peers,
+                    size_t old_capacity, const uint32_t* d_new_offsets, const uint32_t* d_new_peers,
+                    size_t new_capacity, uint32_t* d_ent_offsets, uint32_t* d_ent_peers, size_t ent_capacity,
+                    uint32_t* d_left_offsets, uint32_t* d_left_peers, size_t left_capacity,
+                    wq_diff_counters* d_counters, bool own);
+void csr_diff_release(wq_router* h);
 // wq_multi.hip: the multi-GPU handle's side of the entry points (h->multi != nullptr)
 int multi_merge_any(wq_router* h);
 int multi_apply_ops(wq_router* h, const wq_op* ops, size_t n);

@@ -133,6 +133,7 @@ int wq_router_destroy(wq_router* h) {
     (void)hipStreamSynchronize(h->stream);
     shard_release(h);
     follow_release(h);
+    csr_diff_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
         for (auto e : *v) (void)hipEventDestroy(e);
     DevBuf* bufs[] = {&h->st.h, &h->st.w, &h->st.kx, &h->st.ky, &h->st.kz, &h->st.p,
@@ -657,6 +658,87 @@ int wq_peer_major_device(wq_router* h, const uint32_t* d_offsets, const uint32_t
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_peer_major(h, d_offsets, d_peers, n_msgs, n_pairs, d_connected, n_peers, d_peer_offsets,
                              d_msgs_out);
+}
+
+// The argument rules both forms of wq_csr_diff share (capacities already clamped to 2^32 - 1).
+static bool csr_diff_args_ok(const uint32_t* old_off, const uint32_t* old_peers, size_t old_cap, const uint32_t* new_off,
+                             const uint32_t* new_peers, size_t new_cap, const uint32_t* ent_off,
+                             const uint32_t* ent_peers, size_t ent_cap, const uint32_t* left_off,
+                             const uint32_t* left_peers, size_t left_cap) {
+    if (!old_off || !new_off || !ent_off) return false;
+    if ((old_cap && !old_peers) || (new_cap && !new_peers) || (ent_cap && !ent_peers)) return false;
+    if (!left_off) return !left_peers && left_cap == 0;  // the left side is given whole or not at all
+    return !(left_cap && !left_peers);
+}
+
+int wq_csr_diff_device(wq_router* h, size_t n_rows, const uint32_t* d_old_offsets, const uint32_t* d_old_peers,
+                       size_t old_capacity, const uint32_t* d_new_offsets, const uint32_t* d_new_peers,
+                       size_t new_capacity, uint32_t* d_ent_offsets, uint32_t* d_ent_peers, size_t ent_capacity,
+                       uint32_t* d_left_offsets, uint32_t* d_left_peers, size_t left_capacity,
+                       wq_diff_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!csr_diff_args_ok(d_old_offsets, d_old_peers, old_capacity, d_new_offsets, d_new_peers, new_capacity,
+                          d_ent_offsets, d_ent_peers, ent_capacity, d_left_offsets, d_left_peers, left_capacity))
+        return set_error(h, WQ_E_INVALID, "csr_diff: a null array with a non-zero size, or half a left side");
+    if (n_rows >= 0xFFFFFC00ull) return set_error(h, WQ_E_INVALID, "n_rows must be < 2^32 - 1024");
+    const size_t lim = 0xFFFFFFFFull;  // u32 CSR offsets
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_csr_diff(h, n_rows, d_old_offsets, d_old_peers, std::min(old_capacity, lim), d_new_offsets,
+                           d_new_peers, std::min(new_capacity, lim), d_ent_offsets, d_ent_peers,
+                           std::min(ent_capacity, lim), d_left_offsets, d_left_peers, std::min(left_capacity, lim),
+                           d_counters, false);
+}
+
+int wq_csr_diff(wq_router* h, size_t n_rows, const uint32_t* old_offsets, const uint32_t* old_peers,
+                size_t old_capacity, const uint32_t* new_offsets, const uint32_t* new_peers, size_t new_capacity,
+                uint32_t* ent_offsets, uint32_t* ent_peers, size_t ent_capacity, uint32_t* left_offsets,
+                uint32_t* left_peers, size_t left_capacity, size_t* n_entered, size_t* n_left) {
+    if (!h) return WQ_E_INVALID;
+    if (!n_entered || (left_offsets && !n_left) ||
+        !csr_diff_args_ok(old_offsets, old_peers, old_capacity, new_offsets, new_peers, new_capacity, ent_offsets,
+                          ent_peers, ent_capacity, left_offsets, left_peers, left_capacity))
+        return set_error(h, WQ_E_INVALID, "csr_diff: a null array with a non-zero size, or half a left side");
+    if (n_rows >= 0xFFFFFC00ull) return set_error(h, WQ_E_INVALID, "n_rows must be < 2^32 - 1024");
+    const size_t lim = 0xFFFFFFFFull;
+    const size_t M = n_rows, co = std::min(old_capacity, lim), cn = std::min(new_capacity, lim),
+                 ce = std::min(ent_capacity, lim), cl = std::min(left_capacity, lim);
+    WQ_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t ob = (M + 1) * 4;
+    const size_t i_oo = 0, i_op = align256(i_oo + ob), i_no = align256(i_op + co * 4), i_np = align256(i_no + ob),
+                 n_in = align256(i_np + cn * 4);
+    WQ_ALLOC(h, h->h_in, n_in + 256);
+    char* din = h->h_in.as<char>();
+    WQ_HIP(h, hipMemcpyAsync(din + i_oo, old_offsets, ob, hipMemcpyHostToDevice, s));
+    if (co) WQ_HIP(h, hipMemcpyAsync(din + i_op, old_peers, co * 4, hipMemcpyHostToDevice, s));
+    WQ_HIP(h, hipMemcpyAsync(din + i_no, new_offsets, ob, hipMemcpyHostToDevice, s));
+    if (cn) WQ_HIP(h, hipMemcpyAsync(din + i_np, new_peers, cn * 4, hipMemcpyHostToDevice, s));
+    const size_t o_eo = 0, o_ep = align256(o_eo + ob), o_lo = align256(o_ep + ce * 4), o_lp = align256(o_lo + ob),
+                 n_out = align256(o_lp + cl * 4);
+    WQ_ALLOC(h, h->h_out, n_out + 256);
+    char* dout = h->h_out.as<char>();
+    auto u32p = [](char* p) { return reinterpret_cast<uint32_t*>(p); };
+    int rc = launch_csr_diff(h, M, u32p(din + i_oo), co ? u32p(din + i_op) : nullptr, co, u32p(din + i_no),
+                             cn ? u32p(din + i_np) : nullptr, cn, u32p(dout + o_eo), ce ? u32p(dout + o_ep) : nullptr, ce,
+                             left_offsets ? u32p(dout + o_lo) : nullptr,
+                             (left_offsets && cl) ? u32p(dout + o_lp) : nullptr, left_offsets ? cl : 0, nullptr, true);
+    if (rc) return rc;
+    wq_diff_counters cnt;
+    WQ_HIP(h, hipMemcpyAsync(&cnt, h->diff_err.as<char>() + 16, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    WQ_HIP(h, hipStreamSynchronize(s));
+    *n_entered = cnt.n_entered;
+    if (n_left) *n_left = cnt.n_left;
+    WQ_HIP(h, hipMemcpyAsync(ent_offsets, dout + o_eo, ob, hipMemcpyDeviceToHost, s));
+    if (left_offsets) WQ_HIP(h, hipMemcpyAsync(left_offsets, dout + o_lo, ob, hipMemcpyDeviceToHost, s));
+    if (!cnt.overflow) {
+        if (cnt.n_entered) WQ_HIP(h, hipMemcpyAsync(ent_peers, dout + o_ep, cnt.n_entered * 4, hipMemcpyDeviceToHost, s));
+        if (left_offsets && cnt.n_left)
+            WQ_HIP(h, hipMemcpyAsync(left_peers, dout + o_lp, cnt.n_left * 4, hipMemcpyDeviceToHost, s));
+    }
+    WQ_HIP(h, hipStreamSynchronize(s));
+    if (cnt.overflow)
+        return set_error(h, WQ_E_CAPACITY, "csr_diff output capacity too small (required sizes in *n_entered, *n_left)");
+    return WQ_OK;
 }
 
 int wq_is_subscribed(wq_router* h, size_t n, const uint32_t* world, const uint32_t* peer, int key_is_raw,

@@ -1,0 +1,194 @@
+"""Interest changes between two ticks: who entered and who left each row (include/wq_router.h,
+wq_csr_diff*; kernels: csrc/wq_csr_diff.hip).
+
+`csr_diff_np` is the host reference and the byte-identical definition of the GPU output;
+`clamp_csr_np` is the definition of how the kernels read offsets that do not describe a CSR;
+`InterestTracker` is the convenience a server that replicates entities uses: route a tick, get the
+observers that entered and left every entity's interest set since the previous tick.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import abi
+
+
+def _row_keys(offsets: np.ndarray, peers: np.ndarray):
+    """(row << 32 | peer) of every element of a CSR: ascending, because rows are and peers within a
+    row are."""
+    M = len(offsets) - 1
+    counts = np.diff(offsets.astype(np.int64))
+    if (counts < 0).any() or (M >= 0 and len(offsets) and int(offsets[0]) != 0):
+        raise ValueError("offsets must ascend from 0 (clamp_csr_np makes them)")
+    rows = np.repeat(np.arange(M, dtype=np.uint64), counts)
+    return rows, (rows << np.uint64(32)) | peers[: int(offsets[-1])].astype(np.uint64)
+
+
+def _missing(keys: np.ndarray, other: np.ndarray) -> np.ndarray:
+    """keys[i] not in other (both ascending and distinct)."""
+    if len(other) == 0:
+        return np.ones(len(keys), bool)
+    at = np.searchsorted(other, keys)
+    return other[np.minimum(at, len(other) - 1)] != keys
+
+
+def _side(rows, keys, other_keys, peers, M):
+    keep = _missing(keys, other_keys)
+    out_peers = np.ascontiguousarray(peers[: len(keys)][keep], dtype=np.uint32)
+    offsets = np.zeros(M + 1, dtype=np.uint32)
+    np.cumsum(np.bincount(rows[keep].astype(np.int64), minlength=M)[:M], out=offsets[1:])
+    return offsets, out_peers
+
+
+def csr_diff_np(old_offsets, old_peers, new_offsets, new_peers):
+    """(ent_offsets, ent_peers, left_offsets, left_peers) of two CSRs over the same rows, peers
+    ascending and distinct within a row: row m of entered = new_m \\ old_m, of left = old_m \\ new_m,
+    both ascending. All four arrays are uint32."""
+    oo = np.ascontiguousarray(old_offsets, dtype=np.uint32)
+    no = np.ascontiguousarray(new_offsets, dtype=np.uint32)
+    op = np.ascontiguousarray(old_peers, dtype=np.uint32)
+    npr = np.ascontiguousarray(new_peers, dtype=np.uint32)
+    if len(oo) != len(no) or len(oo) < 1:
+        raise ValueError("both CSRs need offsets[n_rows + 1] over the same rows")
+    M = len(oo) - 1
+    ro, ko = _row_keys(oo, op)
+    rn, kn = _row_keys(no, npr)
+    eo, ep = _side(rn, kn, ko, npr, M)
+    lo, lp = _side(ro, ko, kn, op, M)
+    return eo, ep, lo, lp
+
+
+def diff_limit(capacity: int) -> int:
+    """csr_diff_ops.hpp diff_limit: the elements a side's clamped rows are walked up to."""
+    return min((2 * capacity + 63) & ~63, 0xFFFFFFC0)
+
+
+def clamp_csr_np(offsets, peers, capacity: int | None = None):
+    """How wq_csr_diff* reads a CSR whose offsets may not describe one (csr_diff_ops.hpp): row m is
+    the part of [offsets[m], offsets[m + 1]) inside [0, capacity), empty when offsets[m + 1] <
+    offsets[m]; the rows are walked up to diff_limit(capacity) elements in total. Returns (offsets,
+    peers, cut): a valid CSR holding those rows, and whether any row was cut (error bit 0)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).astype(np.int64)
+    peers = np.ascontiguousarray(peers, dtype=np.uint32)
+    cap = len(peers) if capacity is None else int(capacity)
+    a = np.minimum(off[:-1], cap)
+    b = np.maximum(a, np.minimum(off[1:], cap))
+    cut = bool(((off[1:] < off[:-1]) | (off[1:] > cap)).any())
+    pre = np.concatenate([[0], np.cumsum(b - a)])
+    pre = np.minimum(pre, diff_limit(cap))
+    n = np.diff(pre)
+    idx = np.repeat(a - pre[:-1], n) + np.arange(int(pre[-1]), dtype=np.int64)
+    return pre.astype(np.uint32), np.ascontiguousarray(peers[idx], dtype=np.uint32), cut
+
+
+def peer_major_np(offsets, peers, n_peers: int):
+    """The transpose of a CSR: (peer_offsets[n_peers + 1], rows) — per peer the rows that hold it,
+    ascending (what wq_peer_major_device writes with every peer connected)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+    peers = np.ascontiguousarray(peers, dtype=np.uint32)[: int(offsets[-1])]
+    rows = np.repeat(np.arange(len(offsets) - 1, dtype=np.uint32), np.diff(offsets.astype(np.int64)))
+    keep = peers < n_peers
+    order = np.argsort(peers[keep], kind="stable")
+    po = np.zeros(n_peers + 1, dtype=np.uint32)
+    np.cumsum(np.bincount(peers[keep].astype(np.int64), minlength=n_peers)[:n_peers], out=po[1:])
+    return po, rows[keep][order]
+
+
+class InterestTracker:
+    """Routes ticks of `n_rows` entities (row m of every tick = entity m) and keeps the previous
+    tick's CSR on the device, so every `route` also returns who entered and who left each row.
+
+    It owns two CSR buffer sets and the two output sets (torch tensors on the router's device, int32
+    holding the u32 bits); a tick is routed into the set that is not the previous one, diffed against
+    the previous one, and the two swap — no CSR is copied. Once per tick it reads the route's and the
+    diff's counters and waits for the device to do so: a convenience, not the asynchronous path
+    (that is Router.route_device + Router.csr_diff_device). A buffer that overflows is grown and the
+    step redone."""
+
+    def __init__(self, router, n_rows: int, capacity: int, with_left: bool = True):
+        import torch
+        self.torch = torch
+        self.router = router
+        self.n_rows = int(n_rows)
+        self.with_left = bool(with_left)
+        self.dev = torch.device("cuda", router.device)
+        cap = max(int(capacity), 1)
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        # [offsets, peers, pairs held]; `prev` starts as the empty CSR: the first tick enters everything
+        self.prev = [torch.zeros(self.n_rows + 1, **i32), torch.empty(cap, **i32), 0]
+        self.cur = [torch.zeros(self.n_rows + 1, **i32), torch.empty(cap, **i32), 0]
+        self.ent = [torch.zeros(self.n_rows + 1, **i32), torch.empty(cap, **i32), 0]
+        self.left = [torch.zeros(self.n_rows + 1, **i32), torch.empty(cap, **i32), 0] if with_left else None
+        self.route_cnt = torch.zeros(24, dtype=torch.uint8, device=self.dev)
+        self.diff_cnt = torch.zeros(24, dtype=torch.uint8, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self.ticks = 0
+
+    def _grow(self, buf, need: int):
+        if need > buf[1].numel():
+            buf[1] = self.torch.empty(need + need // 4, dtype=self.torch.int32, device=self.dev)
+
+    def _read(self, t, dtype):
+        # the handle has a stream of its own: wait for the whole device, then read
+        self.torch.cuda.synchronize(self.dev)
+        return t.cpu().numpy().view(dtype)[0]
+
+    def route(self, pos_ptr: int, world_ptr: int, sender_ptr: int, repl_ptr: int):
+        """One tick of n_rows messages on device pointers. Returns (ent_offsets, ent_peers,
+        left_offsets, left_peers, n_entered, n_left); the tensors are views of the tracker's buffers,
+        valid until the next call; the left ones are None and n_left 0 with with_left=False."""
+        r, M, cur = self.router, self.n_rows, self.cur
+        while True:
+            r.route_device(pos_ptr, world_ptr, sender_ptr, repl_ptr, M, cur[0].data_ptr(), cur[1].data_ptr(), None,
+                           cur[1].numel(), self.route_cnt.data_ptr())
+            c = self._read(self.route_cnt, abi.COUNTERS_DTYPE)
+            if c["error"]:
+                r.check_health()
+                raise RuntimeError(f"route error bits {int(c['error']):#x}")
+            cur[2] = int(c["n_pairs"]) if M else 0
+            if not c["overflow"]:
+                break
+            r.route_health()  # the retried tick's overflow is handled here: clear the sticky word
+            self._grow(cur, cur[2])
+        prev, ent, left = self.prev, self.ent, self.left
+        while True:
+            r.csr_diff_device(M, prev[0].data_ptr(), prev[1].data_ptr(), prev[1].numel(), cur[0].data_ptr(),
+                              cur[1].data_ptr(), cur[1].numel(), ent[0].data_ptr(), ent[1].data_ptr(),
+                              ent[1].numel(), left[0].data_ptr() if left else None,
+                              left[1].data_ptr() if left else None, left[1].numel() if left else 0,
+                              self.diff_cnt.data_ptr())
+            d = self._read(self.diff_cnt, abi.DIFF_COUNTERS_DTYPE)
+            if d["error"]:
+                raise RuntimeError("the diff read a CSR whose offsets do not ascend within its capacity")
+            ent[2] = int(d["n_entered"])
+            if left:
+                left[2] = int(d["n_left"])
+            if not d["overflow"]:
+                break
+            self._grow(ent, ent[2])
+            if left:
+                self._grow(left, left[2])
+        self.prev, self.cur = cur, prev
+        self.ticks += 1
+        return (ent[0], ent[1][: ent[2]], left[0] if left else None, left[1][: left[2]] if left else None,
+                ent[2], left[2] if left else 0)
+
+    def current(self):
+        """(offsets, peers[:P]) of the latest tick's CSR (device tensors, valid until the next call)."""
+        return self.prev[0], self.prev[1][: self.prev[2]]
+
+    def peer_major(self, which: str, connected_ptr: int | None, n_peers: int):
+        """Per observer the entities that entered ("entered") or left ("left") its view in the latest
+        tick: (peer_offsets[n_peers + 1], rows[kept]) through wq_peer_major_device."""
+        torch = self.torch
+        if which not in ("entered", "left") or (which == "left" and not self.left):
+            raise ValueError("which is 'entered' or 'left' (the latter only with with_left=True)")
+        src = self.ent if which == "entered" else self.left
+        po = torch.empty(n_peers + 1, dtype=torch.int32, device=self.dev)
+        rows = torch.empty(max(src[2], 1), dtype=torch.int32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self.router.peer_major_device(src[0].data_ptr(), src[1].data_ptr() if src[2] else None, self.n_rows, src[2],
+                                      connected_ptr, n_peers, po.data_ptr(), rows.data_ptr() if src[2] else None)
+        torch.cuda.synchronize(self.dev)
+        kept = int(po[n_peers].item()) & 0xFFFFFFFF
+        return po, rows[:kept]

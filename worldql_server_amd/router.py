@@ -77,6 +77,9 @@ def load_library(build_if_missing: bool = True):
         "wq_route_global": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_route_global_device": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, vp], i32),
         "wq_peer_major_device": ([vp, vp, vp, sz, sz, vp, u32, vp, vp], i32),
+        "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
+        "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
+                         ctypes.POINTER(sz)], i32),
         "wq_is_subscribed": ([vp, sz, vp, vp, i32, vp, vp], i32),
         "wq_is_subscribed_any": ([vp, sz, vp, vp, vp], i32),
         "wq_world_peers": ([vp, u32, vp, sz, ctypes.POINTER(sz)], i32),
@@ -349,6 +352,51 @@ class Router:
         self._check(self.lib.wq_peer_major_device(self.h, offsets_ptr or None, peers_ptr or None, n_msgs, n_pairs,
                                                   connected_ptr or None, n_peers, peer_offsets_ptr,
                                                   msgs_out_ptr or None))
+
+    # ---- interest changes between two ticks (include/wq_router.h; host reference: interest.py) ----
+    def csr_diff(self, old_offsets, old_peers, new_offsets, new_peers, with_left: bool = True,
+                 ent_capacity: int | None = None, left_capacity: int | None = None):
+        """wq_csr_diff on host arrays: (ent_offsets, ent_peers, left_offsets, left_peers, n_entered,
+        n_left); the left arrays are None and n_left 0 with with_left=False. Without a capacity the
+        outputs are sized to hold any result; with one, a result that does not fit raises WQError
+        (WQ_E_CAPACITY) whose .sizes holds (n_entered, n_left) and .offsets the two offset arrays."""
+        oo = np.ascontiguousarray(old_offsets, dtype=np.uint32)
+        no = np.ascontiguousarray(new_offsets, dtype=np.uint32)
+        op = np.ascontiguousarray(old_peers, dtype=np.uint32)
+        npr = np.ascontiguousarray(new_peers, dtype=np.uint32)
+        if len(oo) != len(no) or len(oo) < 1:
+            raise ValueError("both CSRs need offsets[n_rows + 1] over the same rows")
+        M = len(oo) - 1
+        ce = len(npr) if ent_capacity is None else ent_capacity
+        cl = (len(op) if left_capacity is None else left_capacity) if with_left else 0
+        eo = np.empty(M + 1, dtype=np.uint32)
+        ep = np.empty(max(ce, 1), dtype=np.uint32)
+        lo = np.empty(M + 1, dtype=np.uint32) if with_left else None
+        lp = np.empty(max(cl, 1), dtype=np.uint32) if with_left else None
+        ne, nl = ctypes.c_size_t(), ctypes.c_size_t()
+        rc = self.lib.wq_csr_diff(self.h, M, _p(oo), _p(op) if len(op) else None, len(op), _p(no),
+                                  _p(npr) if len(npr) else None, len(npr), _p(eo), _p(ep) if ce else None, ce,
+                                  _p(lo), _p(lp) if cl else None, cl, ctypes.byref(ne), ctypes.byref(nl))
+        if rc == abi.WQ_E_CAPACITY:
+            err = WQError(rc, self.lib.wq_last_error(self.h).decode())
+            err.sizes = (ne.value, nl.value)
+            err.offsets = (eo, lo)
+            raise err
+        self._check(rc)
+        return eo, ep[: ne.value], lo, (lp[: nl.value] if with_left else None), ne.value, nl.value
+
+    def csr_diff_device(self, n_rows: int, old_offsets_ptr: int, old_peers_ptr: int | None, old_capacity: int,
+                        new_offsets_ptr: int, new_peers_ptr: int | None, new_capacity: int, ent_offsets_ptr: int,
+                        ent_peers_ptr: int | None, ent_capacity: int, left_offsets_ptr: int | None = None,
+                        left_peers_ptr: int | None = None, left_capacity: int = 0,
+                        counters_ptr: int | None = None) -> None:
+        """wq_csr_diff_device: asynchronous on the handle's stream; the counters (abi.DIFF_COUNTERS_DTYPE)
+        stay where counters_ptr points."""
+        self._check(self.lib.wq_csr_diff_device(self.h, n_rows, old_offsets_ptr or None, old_peers_ptr or None,
+                                                old_capacity, new_offsets_ptr or None, new_peers_ptr or None,
+                                                new_capacity, ent_offsets_ptr or None, ent_peers_ptr or None,
+                                                ent_capacity, left_offsets_ptr or None, left_peers_ptr or None,
+                                                left_capacity, counters_ptr or None))
 
     # ---- multi-GPU (cube-hash ownership: wq_sharded.hip) ----
     def shard_ops(self, ops: np.ndarray, n_shards: int) -> np.ndarray:
