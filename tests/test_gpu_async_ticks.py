@@ -1,5 +1,5 @@
 """Asynchronous sharded ticks back to back (wq_sharded_route_tick_async,
-wq_sharded_route_owner_slots_async; csrc/wq_sharded.hip), G = 8 hub shards on cuda:0.
+wq_sharded_route_owner_slots_async; csrc/wq_sharded_slots.hip), G = 8 hub shards on cuda:0.
 
 The reference owns the table in one task and handles every event in order (thread.rs:113-148): every
 tick's result must arrive, in order, and be the one table's. The asynchronous forms end a tick without

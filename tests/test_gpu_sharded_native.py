@@ -1,4 +1,4 @@
-"""The multi-GPU tick behind the C ABI (wq_sharded_route_tick_device, csrc/wq_sharded.hip) against
+"""The multi-GPU tick behind the C ABI (wq_sharded_route_tick_device, csrc/wq_sharded.hip, wq_sharded_slots.hip) against
 the oracle holding the WHOLE table (sharding must not change any result).
 
 Both return forms: "slots" (default — 20-byte slots out, row references plus one pool of cube lists

@@ -1,7 +1,7 @@
 """Cube-hash ownership: the owner function and the message grouping of the
 multi-GPU path, against the oracle's restatements.
 
-The sharded tick itself is native (csrc/wq_sharded.hip) and runs on the GPU only; its parity tests are
+The sharded tick itself is native (csrc/wq_sharded_slots.hip, wq_sharded.hip) and runs on the GPU only; its parity tests are
 tests/test_gpu_sharded_native.py (hub G in {1, 2, 3, 5}, two processes over a gloo all-to-all through
 wq_shard_attach_exchange, RCCL) and tests/test_gpu_g8.py (G = 8). The round-1 Python driver of the
 expanded form (worldql_server_amd/sharded.py) was retired in round 5: nothing of the product used it.

@@ -1,4 +1,4 @@
-// route_async.hpp — the end of an asynchronous sharded tick (wq_sharded.hip): the small exchange
+// route_async.hpp — the end of an asynchronous sharded tick (wq_sharded_slots.hip): the small exchange
 // vectors' layout, and the snapshot that stands in for the end-of-tick read. The tick's tile scan
 // runs it in its own block when it takes the whole scan (tile_scan_kernel, route_scan.hpp), so an
 // asynchronous tick ends without a launch of its own; otherwise k_async_result does.

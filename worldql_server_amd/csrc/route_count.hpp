@@ -62,7 +62,7 @@ constexpr uint32_t kStDone = 0, kStProbe = 1, kStVerify = 2;
 // round) and its peer chunks 2-7 are handed back in peers_out (FULL only; valid for inline records).
 // OWN (the sharded tick's ingesting GPU, route_common.hpp RouteIn::own_*): only the messages whose
 // cube this shard owns are counted; every other message gets e = 0 here (its row comes back from
-// its owner, wq_sharded.hip).
+// its owner, wq_sharded_slots.hip).
 template <bool RAW_KEYS, int IPT, int DBG = 0, bool FULL = false, bool SLOTS = false, bool OWN = false>
 __device__ __forceinline__ void count_rows(const RouteIn& in, const TableView& tv, uint32_t m0,
                                            uint32_t (&e_out)[IPT], uint2 (&inf_out)[IPT], uint64_t& F_local,
@@ -144,7 +144,7 @@ __device__ __forceinline__ void count_rows(const RouteIn& in, const TableView& t
             if (OWN) {
                 const uint32_t ow = shard_of(w, x, y, z, in.own_G);
                 valid = valid && ow == in.own_me;
-                // OWN callers that also group the other shards' messages (wq_sharded.hip
+                // OWN callers that also group the other shards' messages (wq_sharded_slots.hip
                 // own_count_hist_kernel): the owner, bit 31 = a two-slot (unpacked) key
                 if (owner_out) owner_out[i] = ow | (reg ? 0u : 0x80000000u);
             }

@@ -24,7 +24,7 @@ struct EmitParams {
     uint32_t n_blocks = 0;  // emit_map_kernel: 256-message blocks (grid stride when > gridDim.x)
     uint32_t msg_base = 0;  // emit_map_kernel: msgs[] = msg_base + the message's index here (a chunk's first message)
     // emit_map_kernel in the sharded tick: rows whose info.x carries kLocPool read the received
-    // cube-list pool at that word offset (wq_sharded.hip); nullptr everywhere else
+    // cube-list pool at that word offset (wq_sharded_slots.hip); nullptr everywhere else
     const uint32_t* pool = nullptr;
     // emit_map_kernel: OnlySelf rows read the sender at sender[m * sender_stride] (the owner form
     // of the sharded tick routes received slots: their sender is word 3 of 5)

@@ -1,6 +1,6 @@
 // route_gather.hpp — rows of words gathered from anywhere into one contiguous output.
 //
-// The sharded tick (wq_sharded.hip) describes every message's recipients, and every cube list an
+// The sharded tick (wq_sharded_slots.hip) describes every message's recipients, and every cube list an
 // owner ships to another GPU, as a row descriptor {len, skip, pointer}: output word k of the row
 // is src[k + (k >= skip)] — the cube's list or a record's inline peers with the sender's own
 // entry skipped (ExceptSelf), a list copied into a received pool, or the sender itself

@@ -153,7 +153,7 @@ struct ProfileEvents {
     bool enabled = false;
 };
 
-struct ShardCtx;  // wq_sharded.hip: the exchange a sharded tick uses, and its workspace
+struct ShardCtx;  // shard_ctx.hpp: the exchange a sharded tick uses, and its workspace
 struct MultiCtx;  // wq_multi.hip: a handle over G GPUs (wq_router_create_multi)
 
 }  // namespace wq
@@ -273,6 +273,24 @@ uint32_t route_tiles_per_block(uint32_t tiles);
 // The tick's counter slots (this call's, the next call's); *cur == nullptr when M == 0 (offsets[0]
 // and both slots zeroed, nothing left to launch).
 int route_counters(wq_router* h, size_t M, uint32_t* d_offsets, wq_route_counters** cur, wq_route_counters** nxt);
+int launch_route(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
+                 const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t* d_offsets,
+                 uint32_t* d_peers, uint32_t* d_msgs, size_t capacity);
+// wq_shard.hip (what each computes: at its definition)
+struct SlotLayout;  // route_common.hpp
+int launch_shard_messages(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
+                          const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t G, wq_msg_rec* d_out,
+                          uint32_t* d_counts);
+int launch_budget_slots(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
+                        const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t G, uint32_t me,
+                        const SlotLayout& L, uint32_t* d_slots, uint32_t* d_perm, uint32_t* d_a, int phases,
+                        bool hist_ready = false, bool own_too = false, uint32_t* own_slots = nullptr,
+                        uint32_t* own_perm = nullptr, uint32_t* zero_e = nullptr, bool row_any = false,
+                        uint32_t own_budget = 0xFFFFFFFFu, uint32_t* a_self = nullptr);
+uint32_t budget_slot_tile();
+int launch_route_records(wq_router* h, const wq_msg_rec* d_recs, size_t M, uint32_t* d_offsets, uint32_t* d_peers,
+                         uint32_t* d_msgs, size_t capacity);
+int launch_op_owner(wq_router* h, const wq_op* d_ops, size_t n, uint32_t G, uint32_t* d_owner);
 // wq_table.hip
 // ops on the host (copied to h->d_ops) or, with on_device, a device array the batch is read from
 // (validated on the device: no REMOVE_PEER, no reserved world id).
@@ -297,7 +315,7 @@ int table_materialize(wq_router* h);
 // Rebuilds the any-keys if incremental updates left them stale.
 int table_ensure_any(wq_router* h);
 int set_error(wq_router* h, int code, const char* what, hipError_t e = hipSuccess);
-// wq_sharded.hip: frees the exchange and its workspace (destroys an RCCL communicator).
+// wq_shard_exchange.hip: frees the exchange and its workspace (destroys an RCCL communicator).
 void shard_release(wq_router* h);
 // wq_follow.hip: frees the follow state and its scratch.
 void follow_release(wq_router* h);

@@ -5,7 +5,7 @@
 // by the select! loop at :122-146). wq_router_create_multi[_mode] gives that task one handle again:
 // inside, G sub-handles (one per device) and G worker threads — one per sub-handle, since a sharded
 // tick is collective — that the calling thread hands each call to and waits for. Two layouts:
-//   WQ_MULTI_CUBE_HASH  every (world, cube) bucket lives on one shard (cube-hash owner, wq_sharded.hip);
+//   WQ_MULTI_CUBE_HASH  every (world, cube) bucket lives on one shard (cube-hash owner, wq_sharded_slots.hip);
 //                       the sub-handles share an in-process hub and a tick is the sharded tick
 //   WQ_MULTI_REPLICATE  every device holds the whole table (288 GB of HBM holds C3's ~10 GB many
 //                       times over) and routes its own slice of the messages with the single-GPU

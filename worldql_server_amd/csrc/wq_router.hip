@@ -9,21 +9,12 @@
 #include "wq_internal.hpp"
 
 namespace wq {
-int launch_route(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
-                 const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t* d_offsets,
-                 uint32_t* d_peers, uint32_t* d_msgs, size_t capacity);
 int launch_quantize(hipStream_t s, const double* d_in, size_t n, uint16_t cube_size, int64_t* d_out);
 int launch_is_subscribed(wq_router* h, const uint32_t* d_w, const uint32_t* d_p, int raw, const void* d_kp,
                          uint32_t n, uint8_t* d_out);
 int launch_is_subscribed_any(wq_router* h, const uint32_t* d_w, const uint32_t* d_p, uint32_t n, uint8_t* d_out);
 int launch_world_range(wq_router* h, uint32_t w, uint64_t* d_out);
 int launch_low32(wq_router* h, const uint64_t* d_in, uint64_t n, uint32_t* d_out);
-int launch_shard_messages(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
-                          const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t G, wq_msg_rec* d_out,
-                          uint32_t* d_counts);
-int launch_op_owner(wq_router* h, const wq_op* d_ops, size_t n, uint32_t G, uint32_t* d_owner);
-int launch_route_records(wq_router* h, const wq_msg_rec* d_recs, size_t M, uint32_t* d_offsets, uint32_t* d_peers,
-                         uint32_t* d_msgs, size_t capacity);
 int launch_peer_major(wq_router* h, const uint32_t* d_offsets, const uint32_t* d_peers, size_t M, size_t P,
                       const uint32_t* d_connected, uint32_t n_peers, uint32_t* d_peer_offsets, uint32_t* d_msgs_out);
 int launch_route_global(wq_router* h, const uint32_t* d_world, const uint32_t* d_sender, const uint8_t* d_repl,

@@ -5,7 +5,7 @@
 //   (1) shard_messages: quantise each ingested message (kernel 1), compute its owner, and group
 //       the messages by owner into 40-byte records, stable in message order (three launches:
 //       per-block owner histograms -> one flat scan -> ballot-ranked scatter);
-//   (2) an all-to-all of the records (wq_sharded.hip's exchange: RCCL, the hub, or the caller's
+//   (2) an all-to-all of the records (wq_shard_exchange.hip: RCCL, the hub, or the caller's
 //       transport through wq_shard_attach_exchange);
 //   (3) route_records: the single-GPU route (count / scan / emit) on the received records —
 //       keys are already quantised, so the count pass takes its raw-key branch;
@@ -64,7 +64,7 @@ __device__ __forceinline__ void msg_key(const ShardIn& in, uint32_t m, int64_t& 
     }
 }
 
-// Compact records (COMPACT = true; the sharded tick of wq_sharded.hip with the radius filter off):
+// Compact records (COMPACT = true; the sharded tick of wq_sharded_slots.hip with the radius filter off):
 // 20-byte slots of five words. A message whose cube has a packed key (pack_key: the regular case)
 // takes one slot
 //   {pk lo, pk hi, ext, sender, repl | kSlotReg << 8}
@@ -312,7 +312,7 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
-// ---- budgeted slots (the sharded tick of wq_sharded.hip) ----------------------------------------
+// ---- budgeted slots (the sharded tick of wq_sharded_slots.hip) ----------------------------------
 // Only messages owned by ANOTHER shard become slots: the ingesting shard counts the messages of its
 // own cubes in place (count_kernel<..., OWN>). Owner d's slots go to the segment
 // [L.base[d], L.base[d] + L.budget[d]) of the send buffer — sizes fixed on the host before the tick
@@ -783,10 +783,6 @@ __global__ void unpack_records_kernel(const wq_msg_rec* __restrict__ r, uint32_t
     repl[m] = x.repl;
 }
 
-int launch_route(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
-                 const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t* d_offsets,
-                 uint32_t* d_peers, uint32_t* d_msgs, size_t capacity);
-
 int launch_shard_messages(wq_router* h, const double* d_pos, const int64_t* d_keys, const uint32_t* d_world,
                           const uint32_t* d_sender, const uint8_t* d_repl, size_t M, uint32_t G, wq_msg_rec* d_out,
                           uint32_t* d_counts) {
@@ -927,7 +923,7 @@ int launch_budget_slots(wq_router* h, const double* d_pos, const int64_t* d_keys
         WQ_ALLOC(h, h->shard_hist, (uint64_t)in.nblk * G * 4);
         uint32_t* hist = h->shard_hist.as<uint32_t>();
         if (hist_ready) {
-            // the caller's own-cube count wrote it (wq_sharded.hip own_count_hist_kernel)
+            // the caller's own-cube count wrote it (wq_sharded_slots.hip own_count_hist_kernel)
         } else if (d_keys)
             hipLaunchKernelGGL((slot_count_kernel<true>), dim3(in.nblk), dim3(kBlock), 0, s, in, hist);
         else

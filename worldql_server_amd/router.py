@@ -398,7 +398,7 @@ class Router:
                                                 ent_capacity, left_offsets_ptr or None, left_peers_ptr or None,
                                                 left_capacity, counters_ptr or None))
 
-    # ---- multi-GPU (cube-hash ownership: wq_sharded.hip) ----
+    # ---- multi-GPU (cube-hash ownership: wq_shard.hip, wq_sharded*.hip) ----
     def shard_ops(self, ops: np.ndarray, n_shards: int) -> np.ndarray:
         """Owner shard of each op (abi.SHARD_ALL for REMOVE_PEER)."""
         ops = np.ascontiguousarray(ops, dtype=abi.OP_DTYPE)
