@@ -581,6 +581,95 @@ int wq_csr_diff(wq_router* h, size_t n_rows,
                 uint32_t* left_offsets, uint32_t* left_peers, size_t left_capacity,
                 size_t* n_entered, size_t* n_left);
 
+/* ---- record store: RecordCreate / RecordRead / RecordDelete ----
+ * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
+ * Here the spatial index of the records lives in the handle: one row per stored record holding its
+ * region, table, uuid, time and the caller's `handle`. The record's text and bytes (data, flex, the
+ * exact x, y, z) stay with the caller under that handle; the GPU never sees them.
+ *
+ * A store is configured like DatabaseClient (args.rs:194-224): region sizes >= 1 and a table size
+ * that each of them divides, else WQ_E_INVALID. The region of a position is clamp_region_coord per
+ * axis (world_region.rs:18-35, 93-110) and the table of a region clamp_table_size of its minimum
+ * corner (world_region.rs:112-129).
+ *
+ *   - Times are microseconds given by the caller per op; "no after" is INT64_MIN.
+ *   - The store numbers every op it ever received. Among rows of one uuid with equal times the one
+ *     with the higher number is "met later" (record_read.rs:61-81) and is the one a read returns.
+ *     PostgreSQL leaves that order open; this is parity with the restatement in records.py.
+ *   - Ops of one batch act in op order: a delete removes the matching rows with a lower number,
+ *     creates earlier in the same batch included, later ones not.
+ *   - Every query of one read call is answered from the store as it was when the call began, and all
+ *     of the call's dedupe deletions apply afterwards (the reference dedupes "in background"). This
+ *     differs from the reference's one-query-at-a-time loop in one case: two queries of one call read
+ *     different regions of one table that hold the same uuid with different times; the stale copy is
+ *     still returned once. Single-query calls reproduce the sequential reference exactly.
+ *   - A reply row lists its records by ascending (uuid_hi, uuid_lo) (the reference's HashMap order
+ *     is random).
+ *   - Limits: a position is packable when every axis's region index (region minimum / region size)
+ *     lies in [-2^23, 2^23) and the world id is < 2^24 - 1. Ops and queries that are not packable or
+ *     hold a NaN coordinate are rejected and counted, never stored or answered; a rejected query
+ *     gets an empty row. Rows are appended and never moved: a dead row's slot is not reused. The
+ *     regions of one read call together hold fewer than 2^32 - 64 rows, a region counted once per
+ *     query that asks it (the offsets are u32); a call past that returns WQ_E_CAPACITY, answers
+ *     nothing and kills nothing: split it. A multi-GPU handle has no record store (WQ_E_INVALID). */
+#define WQ_RECORD_CREATE 0u /* DatabaseClient::insert_records, database/client.rs + query_constants.rs */
+#define WQ_RECORD_DELETE 1u /* DatabaseClient::delete_records, query_delete_record */
+#define WQ_RECORD_READ_DEDUPE 1u /* flags bit 0: DatabaseClient::dedupe_records, query_delete_duplictes */
+typedef struct wq_rec_op {
+    uint32_t kind; /* WQ_RECORD_CREATE | WQ_RECORD_DELETE */
+    uint32_t world;
+    double pos[3];
+    uint64_t uuid_hi, uuid_lo;
+    int64_t ts_us;   /* create: the row's last_modified; delete: unused */
+    uint32_t handle; /* create: the caller's payload slot; delete: unused */
+    uint32_t reserved;
+} wq_rec_op; /* 64 bytes */
+typedef struct wq_rec_apply_result {
+    uint64_t created, deleted_rows, rejected, rows_live;
+} wq_rec_apply_result;
+typedef struct wq_rec_read_result {
+    uint64_t returned, deduped_rows, rejected;
+    uint64_t scanned;  /* rows of the queried regions the call walked (a region asked twice counts twice) */
+    uint32_t overflow; /* 1: `returned` exceeds the capacity; the pairs past it were not written */
+    uint32_t error;    /* reserved: 0 */
+} wq_rec_read_result;
+
+/* DatabaseClient::new (database/client.rs): opens the handle's (empty) store. */
+int wq_records_open(wq_router* h, uint16_t region_x_size, uint16_t region_y_size, uint16_t region_z_size,
+                    uint32_t table_size);
+int wq_records_close(wq_router* h);
+/* insert_records / delete_records for a batch of ops in op order. wq_records_apply uploads the ops
+ * and waits for the result; wq_records_apply_device reads them from device memory, is asynchronous
+ * on the handle's stream and reads nothing back (d_ops stays valid until the stream has passed the
+ * call; what it created, deleted and rejected is counted in wq_records_totals). */
+int wq_records_apply(wq_router* h, const wq_rec_op* ops, size_t n, wq_rec_apply_result* out);
+int wq_records_apply_device(wq_router* h, const wq_rec_op* d_ops, size_t n);
+/* get_records_in_region + handle_record_read (record_read.rs:43-96) for n queries, and with
+ * WQ_RECORD_READ_DEDUPE dedupe_records for every returned row. after_us may be null (no `after`).
+ * Output: a CSR, offsets[n + 1] and per returned row handles[] and ts_us[]; pairs at index >=
+ * capacity are not written, the offsets are always complete. Both forms wait for the call's totals
+ * (one read at the end); the _device form takes device arrays, `out` is host memory in both. */
+int wq_records_read(wq_router* h, size_t n, const uint32_t* world, const double* pos, const int64_t* after_us,
+                    uint32_t flags, uint32_t* offsets, uint32_t* handles, int64_t* ts_us, size_t capacity,
+                    wq_rec_read_result* out);
+int wq_records_read_device(wq_router* h, size_t n, const uint32_t* d_world, const double* d_pos,
+                           const int64_t* d_after_us, uint32_t flags, uint32_t* d_offsets, uint32_t* d_handles,
+                           int64_t* d_ts_us, size_t capacity, wq_rec_read_result* out);
+/* Handles of the rows killed by deletes and dedupes since the last drain, ascending, so the caller
+ * frees their payload slots. *n is the count; with *n > capacity nothing is drained (WQ_E_CAPACITY). */
+int wq_records_drain_dead(wq_router* h, uint32_t* out, size_t capacity, size_t* n);
+int wq_records_stats(wq_router* h, uint64_t* rows_live, uint64_t* rows_stored, uint64_t* ops_seen);
+/* Counts since wq_records_open, the asynchronous applies included (waits for the stream): nothing an
+ * apply or a read rejected goes uncounted. */
+typedef struct wq_rec_totals {
+    uint64_t created, deleted_rows, deduped_rows, rejected_ops, rejected_queries;
+} wq_rec_totals;
+int wq_records_totals(wq_router* h, wq_rec_totals* out);
+/* clamp_region_coord (world_region.rs:93-110) on the host; WQ_E_INVALID for size 0 or a NaN. */
+int wq_region_quantize(const double* coords, size_t n, uint16_t size, int64_t* out);
+/* clamp_table_size (world_region.rs:112-129) on the host. */
+int wq_table_quantize(const int64_t* region, size_t n, uint32_t table_size, int64_t* out);
+
 /* ---- health of asynchronous ticks ----
  * OR of wq_route_counters.error (error_bits) and of .overflow over every route / global call since
  * the previous wq_route_health on this handle; reading clears them (synchronises the stream). A

@@ -155,6 +155,7 @@ struct ProfileEvents {
 
 struct ShardCtx;  // shard_ctx.hpp: the exchange a sharded tick uses, and its workspace
 struct MultiCtx;  // wq_multi.hip: a handle over G GPUs (wq_router_create_multi)
+struct RecStore;  // wq_records.hip: the record store (wq_records_open)
 
 }  // namespace wq
 
@@ -232,6 +233,7 @@ struct wq_router {
     // call zeroes the next call's) followed by the host form's counters
     wq::DevBuf diff_len, diff_pre, diff_cnt, diff_base, diff_flags, diff_err;
     uint64_t diff_calls = 0;
+    wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
 };
 
 namespace wq {
@@ -327,6 +329,8 @@ int launch_csr_diff(wq_router* h, size_t n_rows, const uint32_t* d_old_offsets, 
                     uint32_t* d_left_offsets, uint32_t* d_left_peers, size_t left_capacity,
                     wq_diff_counters* d_counters, bool own);
 void csr_diff_release(wq_router* h);
+// wq_records.hip: frees the record store.
+void records_release(wq_router* h);
 // wq_multi.hip: the multi-GPU handle's side of the entry points (h->multi != nullptr)
 int multi_merge_any(wq_router* h);
 int multi_apply_ops(wq_router* h, const wq_op* ops, size_t n);

@@ -1,0 +1,520 @@
+"""The record store: RecordCreate / RecordRead / RecordDelete (include/wq_router.h, wq_records.hip).
+
+`RecordStoreRef` is the definition in plain Python — the reference's DatabaseClient
+(worldql_server/src/database/client.rs, world_region.rs, query_constants.rs) and
+handle_record_read (processing/record_read.rs) restated, with what the reference leaves open
+fixed as the header says. `GpuRecordStore` is the ctypes binding of the wq_records_* calls and
+`RecordProcessor` the host side of the three instructions around it.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+
+from . import abi
+from .world_names import GLOBAL_WORLD, SanitizeError, WorldIds, sanitize_world_name
+
+CREATE, DELETE = 0, 1            # WQ_RECORD_CREATE / WQ_RECORD_DELETE
+READ_DEDUPE = 1                  # WQ_RECORD_READ_DEDUPE
+NO_AFTER = -(1 << 63)            # INT64_MIN: no `after`
+I64_MAX = (1 << 63) - 1
+AXIS_BIAS = 1 << 23              # wq_device.hpp kAxisBias
+MAX_PACKED_WORLD = (1 << 24) - 2  # wq_device.hpp kMaxPackedWorld
+MAX_ORDINALS = 0xFFFFFFC0        # record_ops.hpp kRecMaxOrdinals: rows the regions of one read call may hold
+
+REC_OP_DTYPE = np.dtype([("kind", np.uint32), ("world", np.uint32), ("pos", np.float64, (3,)),
+                         ("uuid_hi", np.uint64), ("uuid_lo", np.uint64), ("ts_us", np.int64),
+                         ("handle", np.uint32), ("reserved", np.uint32)])  # struct wq_rec_op
+assert REC_OP_DTYPE.itemsize == 64
+
+
+class RecApplyResult(ctypes.Structure):  # struct wq_rec_apply_result
+    _fields_ = [("created", ctypes.c_uint64), ("deleted_rows", ctypes.c_uint64), ("rejected", ctypes.c_uint64),
+                ("rows_live", ctypes.c_uint64)]
+
+
+class RecTotals(ctypes.Structure):  # struct wq_rec_totals
+    _fields_ = [(f, ctypes.c_uint64) for f in ("created", "deleted_rows", "deduped_rows", "rejected_ops",
+                                                "rejected_queries")]
+
+
+class ReadTooLarge(OverflowError):
+    """The regions of one read call hold 2^32 - 64 rows or more (WQ_E_CAPACITY): split the call."""
+
+
+class RecReadResult(ctypes.Structure):  # struct wq_rec_read_result
+    _fields_ = [("returned", ctypes.c_uint64), ("deduped_rows", ctypes.c_uint64), ("rejected", ctypes.c_uint64),
+                ("scanned", ctypes.c_uint64), ("overflow", ctypes.c_uint32), ("error", ctypes.c_uint32)]
+
+
+# ---- the two quantisers (world_region.rs:93-129) ----
+
+def _sat_i64(c: float) -> int:
+    """Rust's saturating `c as i64` for c >= 0."""
+    return I64_MAX if c >= 9223372036854775808.0 else int(c)
+
+
+def region_coord(c: float, size: int) -> int:
+    """clamp_region_coord: the minimum of c's region. NaN has none (ValueError)."""
+    if math.isnan(c):
+        raise ValueError("NaN has no region")
+    if c == 0.0:
+        return 0
+    if c >= 0.0:
+        ci = _sat_i64(c)
+        return ci - ci % size
+    ci = _sat_i64((-c) + float(size))
+    return -(ci - ci % size)
+
+
+def table_coord(c: int, table_size: int) -> int:
+    """clamp_table_size: multiples stay, the rest goes down on the positive side and to minus the
+    table of (-c) + table_size on the negative one."""
+    if c % table_size == 0:
+        return c
+    if c >= 0:
+        return c - c % table_size
+    nc = -c + table_size
+    return -(nc - nc % table_size)
+
+
+def region_coord_np(coords, size: int) -> np.ndarray:
+    """clamp_region_coord over an array (i64). NaN raises ValueError."""
+    c = np.ascontiguousarray(coords, dtype=np.float64)
+    if np.isnan(c).any():
+        raise ValueError("NaN has no region")
+    neg = c < 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        a = np.where(neg, (-c) + np.float64(size), c)  # one f64 add on the negative side
+        sat = a >= 9223372036854775808.0
+        ci = np.where(sat, I64_MAX, np.where(sat, 0.0, a).astype(np.int64))
+    r = ci - np.fmod(ci, np.int64(size))
+    return np.where(neg, -r, r).astype(np.int64)
+
+
+def table_coord_np(region, table_size: int) -> np.ndarray:
+    """clamp_table_size over an array of i64 (inputs within +-2^62)."""
+    c = np.ascontiguousarray(region, dtype=np.int64)
+    t = np.int64(table_size)
+    rem = np.fmod(c, t)  # truncated, like Rust's %
+    nc = -c + t
+    neg = -(nc - np.fmod(nc, t))
+    return np.where(rem == 0, c, np.where(c >= 0, c - rem, neg)).astype(np.int64)
+
+
+def position_packable(sizes, world: int, pos) -> bool:
+    """The limit of this version: no NaN, every region index in [-2^23, 2^23), world < 2^24 - 1."""
+    if any(math.isnan(float(c)) for c in pos) or world > MAX_PACKED_WORLD:
+        return False
+    return all(-AXIS_BIAS <= region_coord(float(c), s) // s < AXIS_BIAS for c, s in zip(pos, sizes))
+
+
+class RecordStoreRef:
+    """The definition. Rows live in a list; a row is dead once `live` is False. Every op the store
+    receives gets the next sequence number, rejected ones included."""
+
+    def __init__(self, rx: int, ry: int, rz: int, table_size: int):
+        sizes = (int(rx), int(ry), int(rz))
+        if any(s < 1 or s > 0xFFFF for s in sizes) or table_size < 1 or any(table_size % s for s in sizes):
+            raise ValueError("region sizes must be >= 1 and divide the table size")
+        self.sizes, self.table_size = sizes, int(table_size)
+        self.rows: list[dict] = []
+        self.by_region: dict[tuple, list[int]] = {}
+        self.by_table_uuid: dict[tuple, list[int]] = {}
+        self.by_region_uuid: dict[tuple, list[int]] = {}
+        self.ops_seen = 0
+        self.live = 0
+        self.dead: list[int] = []
+        self.totals_ = {"created": 0, "deleted_rows": 0, "deduped_rows": 0, "rejected_ops": 0, "rejected_queries": 0}
+        self.deduped_cross = 0  # rows a dedupe killed in another region than the returned row's
+
+    # -- keys --
+    def region(self, pos) -> tuple:
+        return tuple(region_coord(float(c), s) for c, s in zip(pos, self.sizes))
+
+    def table(self, region) -> tuple:
+        return tuple(table_coord(r, self.table_size) for r in region)
+
+    def packable(self, world: int, pos) -> bool:
+        return position_packable(self.sizes, world, pos)
+
+    def _kill(self, i: int) -> int:
+        row = self.rows[i]
+        if not row["live"]:
+            return 0
+        row["live"] = False
+        self.live -= 1
+        self.dead.append(row["handle"])
+        return 1
+
+    # -- ops --
+    def apply(self, ops) -> dict:
+        """ops: REC_OP_DTYPE records (or dicts with the same fields), applied in order."""
+        created = deleted = rejected = 0
+        for op in ops:
+            seq = self.ops_seen
+            self.ops_seen += 1
+            kind, world = int(op["kind"]), int(op["world"])
+            pos = [float(c) for c in op["pos"]]
+            if kind not in (CREATE, DELETE) or not self.packable(world, pos):
+                rejected += 1
+                continue
+            reg = self.region(pos)
+            uuid = (int(op["uuid_hi"]), int(op["uuid_lo"]))
+            if kind == CREATE:
+                i = len(self.rows)
+                self.rows.append({"world": world, "region": reg, "table": self.table(reg), "uuid": uuid,
+                                  "ts": int(op["ts_us"]), "seq": seq, "handle": int(op["handle"]), "live": True})
+                self.by_region.setdefault((world, reg), []).append(i)
+                self.by_table_uuid.setdefault((world, self.table(reg), uuid), []).append(i)
+                self.by_region_uuid.setdefault((world, reg, uuid), []).append(i)
+                self.live += 1
+                created += 1
+            else:  # every row of (region, uuid) stored so far, whatever its time
+                for i in self.by_region_uuid.pop((world, reg, uuid), ()):
+                    deleted += self._kill(i)
+        for k, v in (("created", created), ("deleted_rows", deleted), ("rejected_ops", rejected)):
+            self.totals_[k] += v
+        return {"created": created, "deleted_rows": deleted, "rejected": rejected, "rows_live": self.live}
+
+    def read(self, queries, dedupe: bool = False, capacity: int | None = None) -> dict:
+        """queries: (world, pos, after_us | None) each. All of them are answered from the store as it
+        is now; the dedupe deletions of every returned row apply afterwards. Returns offsets[n + 1],
+        handles and ts_us (cut at `capacity`), and the counters of wq_rec_read_result."""
+        # the one limit of a call, checked before anything is answered or killed
+        if len(queries) * self.live > MAX_ORDINALS:  # (cheap bound first)
+            counts, total = {}, 0
+            for w, p, _ in queries:
+                p = [float(c) for c in p]
+                if not self.packable(int(w), p):
+                    continue
+                key = (int(w), self.region(p))
+                if key not in counts:
+                    counts[key] = sum(1 for i in self.by_region.get(key, ()) if self.rows[i]["live"])
+                total += counts[key]
+            if total > MAX_ORDINALS:
+                raise ReadTooLarge(total)
+        offsets, winners, rejected, scanned = [0], [], 0, 0
+        for world, pos, after in queries:
+            pos = [float(c) for c in pos]
+            after = NO_AFTER if after is None else int(after)
+            if not self.packable(int(world), pos):
+                rejected += 1
+                offsets.append(len(winners))
+                continue
+            best: dict[tuple, dict] = {}
+            for i in self.by_region.get((int(world), self.region(pos)), ()):
+                row = self.rows[i]
+                if not row["live"]:
+                    continue
+                scanned += 1
+                if not row["ts"] > after:
+                    continue
+                cur = best.get(row["uuid"])
+                # the row met later wins on equal times: the higher sequence number
+                if cur is None or (row["ts"], row["seq"]) > (cur["ts"], cur["seq"]):
+                    best[row["uuid"]] = row
+            winners.extend(best[u] for u in sorted(best))
+            offsets.append(len(winners))
+        self.totals_["rejected_queries"] += rejected
+        deduped = 0
+        if dedupe:
+            for w in winners:
+                for i in self.by_table_uuid.get((w["world"], w["table"], w["uuid"]), ()):
+                    if self.rows[i]["ts"] < w["ts"]:
+                        k = self._kill(i)
+                        deduped += k
+                        self.deduped_cross += k if self.rows[i]["region"] != w["region"] else 0
+        self.totals_["deduped_rows"] += deduped
+        self._sweep()
+        cap = len(winners) if capacity is None else int(capacity)
+        return {"offsets": np.array(offsets, dtype=np.uint32),
+                "handles": np.array([w["handle"] for w in winners[:cap]], dtype=np.uint32),
+                "ts_us": np.array([w["ts"] for w in winners[:cap]], dtype=np.int64),
+                "returned": len(winners), "deduped_rows": deduped, "rejected": rejected, "scanned": scanned,
+                "overflow": int(len(winners) > cap), "error": 0}
+
+    def _sweep(self):
+        """Drops dead rows from the lookup lists once they outnumber the live ones (speed only)."""
+        if len(self.rows) - self.live <= max(self.live, 1024) or getattr(self, "_swept", 0) == len(self.rows):
+            return
+        self._swept = len(self.rows)
+        for d in (self.by_region, self.by_table_uuid, self.by_region_uuid):
+            for k in list(d):
+                d[k] = [i for i in d[k] if self.rows[i]["live"]]
+                if not d[k]:
+                    del d[k]
+
+    def drain_dead(self) -> np.ndarray:
+        out = np.array(sorted(self.dead), dtype=np.uint32)
+        self.dead = []
+        return out
+
+    def stats(self) -> tuple:
+        """(rows_live, rows_stored, ops_seen)."""
+        return self.live, len(self.rows), self.ops_seen
+
+    def totals(self) -> dict:
+        """Counts since the store was made (wq_records_totals)."""
+        return dict(self.totals_)
+
+
+def make_ops(kind, world, pos, uuid_hi, uuid_lo, ts_us=0, handle=0) -> np.ndarray:
+    """REC_OP_DTYPE array from broadcastable columns (pos: [n, 3])."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    ops = np.zeros(len(pos), dtype=REC_OP_DTYPE)
+    ops["kind"], ops["world"], ops["pos"] = kind, world, pos
+    ops["uuid_hi"], ops["uuid_lo"], ops["ts_us"], ops["handle"] = uuid_hi, uuid_lo, ts_us, handle
+    return ops
+
+
+class GpuRecordStore:
+    """wq_records_* on a Router's handle (one store per handle; single-GPU handles only)."""
+
+    def __init__(self, router, rx: int, ry: int, rz: int, table_size: int):
+        self.router, self.lib, self.h = router, router.lib, router.h
+        router._check(self.lib.wq_records_open(self.h, rx, ry, rz, table_size))
+        self.sizes, self.table_size = (int(rx), int(ry), int(rz)), int(table_size)
+        self.open = True
+
+    def close(self):
+        if self.open and getattr(self.router, "h", None):
+            self.router._check(self.lib.wq_records_close(self.h))
+        self.open = False
+
+    def apply(self, ops) -> dict:
+        ops = np.ascontiguousarray(ops, dtype=REC_OP_DTYPE)
+        res = RecApplyResult()
+        self.router._check(self.lib.wq_records_apply(self.h, ops.ctypes.data_as(ctypes.c_void_p) if len(ops) else None,
+                                                     len(ops), ctypes.byref(res)))
+        return {"created": res.created, "deleted_rows": res.deleted_rows, "rejected": res.rejected,
+                "rows_live": res.rows_live}
+
+    def apply_device(self, ops_ptr: int, n: int) -> None:
+        """wq_records_apply_device: asynchronous on the handle's stream."""
+        self.router._check(self.lib.wq_records_apply_device(self.h, ops_ptr or None, n))
+
+    @staticmethod
+    def _result(res, offsets, handles, ts, capacity) -> dict:
+        k = min(int(res.returned), capacity)
+        return {"offsets": offsets, "handles": handles[:k], "ts_us": ts[:k], "returned": int(res.returned),
+                "deduped_rows": int(res.deduped_rows), "rejected": int(res.rejected), "scanned": int(res.scanned),
+                "overflow": int(res.overflow),
+                "error": int(res.error)}
+
+    def read(self, world, pos, after_us=None, dedupe: bool = False, capacity: int = 0, canary: int = 0) -> dict:
+        """wq_records_read on host arrays with room for `capacity` rows. With canary > 0 that many
+        words follow each output array, and the result's "canaries_ok" says whether they survived."""
+        world = np.ascontiguousarray(world, dtype=np.uint32)
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        n = len(world)
+        after = None if after_us is None else np.ascontiguousarray(after_us, dtype=np.int64)
+        mark32, mark64 = 0xA5A5A5A5, -0x5A5A5A5A5A5A5A5B
+        offsets = np.full(n + 1 + canary, mark32, dtype=np.uint32)
+        handles = np.full(capacity + canary, mark32, dtype=np.uint32)
+        ts = np.full(capacity + canary, mark64, dtype=np.int64)
+        res = RecReadResult()
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = self.lib.wq_records_read(
+            self.h, n, p(world) if n else None, p(pos) if n else None, None if after is None or not n else p(after),
+            READ_DEDUPE if dedupe else 0, p(offsets), p(handles) if capacity else None, p(ts) if capacity else None,
+            capacity, ctypes.byref(res))
+        if rc == abi.WQ_E_CAPACITY:
+            raise ReadTooLarge(self.lib.wq_last_error(self.h).decode())
+        self.router._check(rc)
+        out = self._result(res, offsets[: n + 1], handles[:capacity], ts[:capacity], capacity)
+        k = len(out["handles"])
+        out["canaries_ok"] = bool((offsets[n + 1:] == mark32).all() and (handles[k:] == mark32).all()
+                                  and (ts[k:] == mark64).all())
+        return out
+
+    def read_device(self, n: int, world_ptr: int, pos_ptr: int, after_ptr: int | None, dedupe: bool,
+                    offsets_ptr: int, handles_ptr: int, ts_ptr: int, capacity: int) -> dict:
+        """wq_records_read_device: device arrays in and out; the counters come back as a dict."""
+        res = RecReadResult()
+        rc = self.lib.wq_records_read_device(
+            self.h, n, world_ptr or None, pos_ptr or None, after_ptr or None, READ_DEDUPE if dedupe else 0,
+            offsets_ptr, handles_ptr or None, ts_ptr or None, capacity, ctypes.byref(res))
+        if rc == abi.WQ_E_CAPACITY:
+            raise ReadTooLarge(self.lib.wq_last_error(self.h).decode())
+        self.router._check(rc)
+        return {"returned": int(res.returned), "deduped_rows": int(res.deduped_rows), "rejected": int(res.rejected),
+                "scanned": int(res.scanned), "overflow": int(res.overflow), "error": int(res.error)}
+
+    def drain_dead(self) -> np.ndarray:
+        n = ctypes.c_size_t()
+        rc = self.lib.wq_records_drain_dead(self.h, None, 0, ctypes.byref(n))
+        if rc not in (0, abi.WQ_E_CAPACITY):
+            self.router._check(rc)
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.router._check(self.lib.wq_records_drain_dead(self.h, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                              ctypes.byref(n)))
+        return out
+
+    def stats(self) -> tuple:
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self.router._check(self.lib.wq_records_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def totals(self) -> dict:
+        t = RecTotals()
+        self.router._check(self.lib.wq_records_totals(self.h, ctypes.byref(t)))
+        return {f: int(getattr(t, f)) for f, _ in RecTotals._fields_}
+
+
+def region_quantize(lib, coords, size: int) -> np.ndarray:
+    """wq_region_quantize (host)."""
+    c = np.ascontiguousarray(coords, dtype=np.float64)
+    out = np.zeros(len(c), dtype=np.int64)
+    rc = lib.wq_region_quantize(c.ctypes.data_as(ctypes.c_void_p), len(c), size, out.ctypes.data_as(ctypes.c_void_p))
+    if rc:
+        raise ValueError(f"wq_region_quantize: {rc}")
+    return out
+
+
+def table_quantize(lib, region, table_size: int) -> np.ndarray:
+    """wq_table_quantize (host)."""
+    r = np.ascontiguousarray(region, dtype=np.int64)
+    out = np.zeros(len(r), dtype=np.int64)
+    rc = lib.wq_table_quantize(r.ctypes.data_as(ctypes.c_void_p), len(r), table_size,
+                               out.ctypes.data_as(ctypes.c_void_p))
+    if rc:
+        raise ValueError(f"wq_table_quantize: {rc}")
+    return out
+
+
+def parse_epoch_millis(parameter: str):
+    """utils/time.rs:6-16: a u64 of epoch milliseconds -> microseconds; None when it does not parse."""
+    s = parameter
+    if s.startswith("+"):
+        s = s[1:]
+    if not s or not all("0" <= ch <= "9" for ch in s):
+        return None
+    ms = int(s)
+    if ms >= 1 << 64 or ms // 1000 > 8_210_298_412_799:  # chrono's NaiveDateTime range
+        return None
+    return ms * 1000
+
+
+class RecordProcessor:
+    """The three record instructions of processing/thread.rs around a store (`GpuRecordStore` or
+    `RecordStoreRef`). The payload of a record (its data, flex and exact position) stays here, in a
+    slab indexed by the `handle` the store keeps; slots of rows the store killed are freed from its
+    dead list. Events are dicts: {"instruction", "world_name", "sender_uuid", "parameter",
+    "position", "records"}, a record {"uuid": (hi, lo), "world_name", "position", "data", "flex"}."""
+
+    def __init__(self, store, worlds: WorldIds | None = None, dedupe: bool = True):
+        self.store = store
+        self.worlds = worlds if worlds is not None else WorldIds()
+        self.dedupe = dedupe
+        self.slab: list = []
+        self.free: list[int] = []
+        self.dropped = 0  # records and reads the reference would have dropped or failed on
+
+    def _slot(self, record) -> int:
+        if self.free:
+            i = self.free.pop()
+            self.slab[i] = record
+            return i
+        self.slab.append(record)
+        return len(self.slab) - 1
+
+    def _ops(self, kind: int, ev, now_us: int) -> list:
+        ops = []
+        for rec in ev.get("records") or ():
+            if rec.get("position") is None:  # insert_records / delete_records: no position, no row
+                self.dropped += 1
+                continue
+            try:
+                world = self.worlds.intern(sanitize_world_name(rec["world_name"]))
+            except SanitizeError:
+                self.dropped += 1
+                continue
+            if not position_packable(self.store.sizes, world, rec["position"]):  # the store would reject it
+                self.dropped += 1
+                continue
+            handle = self._slot(rec) if kind == CREATE else 0
+            ops.append((kind, world, tuple(rec["position"]), rec["uuid"][0], rec["uuid"][1], now_us, handle))
+        return ops
+
+    def process(self, events, now_us: int) -> list:
+        """One batch of decoded events in order. Creates and deletes become one apply per run of
+        them, reads one read call per run of reads. Returns [(sender_uuid, world_name, records)]:
+        one RecordReply per read that found something (record_read.rs:55-58)."""
+        replies, ops, reads = [], [], []
+
+        def flush_ops():
+            if ops:
+                arr = np.zeros(len(ops), dtype=REC_OP_DTYPE)
+                for i, (k, w, p, hi, lo, t, hd) in enumerate(ops):
+                    arr[i] = (k, w, p, hi, lo, t, hd, 0)
+                res = self.store.apply(arr)
+                self.dropped += int(res["rejected"])
+                ops.clear()
+                self._free_dead()
+
+        def read_batch(batch):
+            """The records of every read of `batch`, from one call: one snapshot. A sizing call (no
+            dedupe, no room for rows: it changes nothing) gives the row count, then one call answers and
+            dedupes. A batch the store finds too large for one call is answered in two halves."""
+            world = [r[1] for r in batch]
+            pos = [r[2] for r in batch]
+            after = [NO_AFTER if r[3] is None else r[3] for r in batch]
+            try:
+                if isinstance(self.store, RecordStoreRef):
+                    out = self.store.read(list(zip(world, pos, after)), dedupe=self.dedupe)
+                else:
+                    need = self.store.read(world, pos, after, dedupe=False, capacity=0)["returned"]
+                    out = self.store.read(world, pos, after, dedupe=self.dedupe, capacity=need)
+            except ReadTooLarge:
+                if len(batch) == 1:
+                    raise
+                return read_batch(batch[: len(batch) // 2]) + read_batch(batch[len(batch) // 2:])
+            off = out["offsets"]
+            return [[self.slab[int(hd)] for hd in out["handles"][int(off[i]): int(off[i + 1])]]
+                    for i in range(len(batch))]
+
+        def flush_reads():
+            if not reads:
+                return
+            for (ev, _, _, _), recs in zip(reads, read_batch(list(reads))):
+                if recs:
+                    replies.append((ev["sender_uuid"], ev["world_name"], recs))
+            reads.clear()
+            self._free_dead()
+
+        for ev in events:
+            ins = ev["instruction"]
+            if ins not in ("RecordCreate", "RecordRead", "RecordDelete") or ev["world_name"] == GLOBAL_WORLD:
+                continue
+            if ins == "RecordRead":
+                flush_ops()
+                if ev.get("position") is None:
+                    self.dropped += 1
+                    continue
+                after = None
+                if ev.get("parameter") is not None:
+                    after = parse_epoch_millis(ev["parameter"])
+                    if after is None:  # record_read.rs:31-37: the read is dropped
+                        self.dropped += 1
+                        continue
+                try:
+                    world = self.worlds.intern(sanitize_world_name(ev["world_name"]))
+                except SanitizeError:
+                    self.dropped += 1
+                    continue
+                reads.append((ev, world, tuple(ev["position"]), after))
+            else:
+                flush_reads()
+                ops.extend(self._ops(CREATE if ins == "RecordCreate" else DELETE, ev, now_us))
+        flush_ops()
+        flush_reads()
+        return replies
+
+    def _free_dead(self):
+        for hd in self.store.drain_dead():
+            self.slab[int(hd)] = None
+            self.free.append(int(hd))

@@ -80,6 +80,17 @@ def load_library(build_if_missing: bool = True):
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
+        "wq_records_open": ([vp, u16, u16, u16, u32], i32),
+        "wq_records_close": ([vp], i32),
+        "wq_records_apply": ([vp, vp, sz, vp], i32),
+        "wq_records_apply_device": ([vp, vp, sz], i32),
+        "wq_records_read": ([vp, sz, vp, vp, vp, u32, vp, vp, vp, sz, vp], i32),
+        "wq_records_read_device": ([vp, sz, vp, vp, vp, u32, vp, vp, vp, sz, vp], i32),
+        "wq_records_drain_dead": ([vp, vp, sz, ctypes.POINTER(sz)], i32),
+        "wq_records_stats": ([vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3, i32),
+        "wq_records_totals": ([vp, vp], i32),
+        "wq_region_quantize": ([vp, sz, u16, vp], i32),
+        "wq_table_quantize": ([vp, sz, u32, vp], i32),
         "wq_is_subscribed": ([vp, sz, vp, vp, i32, vp, vp], i32),
         "wq_is_subscribed_any": ([vp, sz, vp, vp, vp], i32),
         "wq_world_peers": ([vp, u32, vp, sz, ctypes.POINTER(sz)], i32),
