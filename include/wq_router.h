@@ -608,7 +608,8 @@ int wq_csr_diff(wq_router* h, size_t n_rows,
  *   - Limits: a position is packable when every axis's region index (region minimum / region size)
  *     lies in [-2^23, 2^23) and the world id is < 2^24 - 1. Ops and queries that are not packable or
  *     hold a NaN coordinate are rejected and counted, never stored or answered; a rejected query
- *     gets an empty row. Rows are appended and never moved: a dead row's slot is not reused. The
+ *     gets an empty row. Rows are appended and never moved until wq_records_vacuum: a dead row's
+ *     slot is not reused, and rows_stored counts the dead until a vacuum drops them. The
  *     regions of one read call together hold fewer than 2^32 - 64 rows, a region counted once per
  *     query that asks it (the offsets are u32); a call past that returns WQ_E_CAPACITY, answers
  *     nothing and kills nothing: split it. A multi-GPU handle has no record store (WQ_E_INVALID). */
@@ -665,6 +666,48 @@ typedef struct wq_rec_totals {
     uint64_t created, deleted_rows, deduped_rows, rejected_ops, rejected_queries;
 } wq_rec_totals;
 int wq_records_totals(wq_router* h, wq_rec_totals* out);
+
+/* ---- record store: vacuum and snapshots ----
+ * One stored row as a snapshot carries it. `region` is the region's minimum corner per axis, as
+ * wq_region_quantize returns it; `seq` the number of the op that created the row. */
+typedef struct wq_rec_row {
+    uint32_t world, handle;
+    int64_t region[3];
+    uint64_t uuid_hi, uuid_lo;
+    int64_t ts_us;
+    uint64_t seq;
+} wq_rec_row; /* 64 bytes */
+typedef struct wq_rec_vacuum_result {
+    uint64_t rows_before, rows_after; /* rows stored */
+    uint64_t bytes_before, bytes_after; /* the row arrays, the dead list and the views */
+} wq_rec_vacuum_result;
+typedef struct wq_rec_import_result {
+    uint64_t imported, rejected;
+} wq_rec_import_result;
+/* Drops the dead rows: the live ones move together in their order (they keep seq, ts_us and handle),
+ * both views are renumbered and every array is reallocated to fit. Nothing a later apply, read,
+ * drain or total returns changes; wq_records_stats then reports rows_stored == rows_live, and the
+ * store's limit of 2^32 - 1 rows counts live rows again. Handles not yet drained stay in the dead
+ * list. Synchronous. A store with nothing dead is left as it is. `out` may be null. */
+int wq_records_vacuum(wq_router* h, wq_rec_vacuum_result* out);
+/* The live rows in row order as wq_rec_row. *n is the live count and *ops_seen the store's op
+ * counter; with *n > capacity nothing is written (WQ_E_CAPACITY), and `out` may be null with
+ * capacity 0 to ask for the count. The store is not changed: no vacuum, and handles not yet drained
+ * are not part of a snapshot. Two exports of one store give the same bytes. The _device form writes
+ * to device memory (16-byte aligned). Both forms wait for the count. */
+int wq_records_export(wq_router* h, wq_rec_row* out, size_t capacity, size_t* n, uint64_t* ops_seen);
+int wq_records_export_device(wq_router* h, wq_rec_row* d_out, size_t capacity, size_t* n, uint64_t* ops_seen);
+/* Builds a store from a snapshot. The store must have received no op and hold no row (else
+ * WQ_E_INVALID); its region and table sizes may differ from the snapshot's source. A row is rejected
+ * and counted when a region[d] is no multiple of that axis's region size, its index is outside
+ * [-2^23, 2^23), the world is not packable or seq >= ops_seen. Accepted rows are stored in the given
+ * order under their own seq; the table is recomputed from the region. Two accepted rows with the same
+ * (world, region, uuid, ts_us, seq) refuse the whole import (WQ_E_INVALID, the store stays empty).
+ * Afterwards the op counter is `ops_seen`, wq_records_totals is all zeros and rows_live == imported.
+ * Synchronous. */
+int wq_records_import(wq_router* h, const wq_rec_row* rows, size_t n, uint64_t ops_seen, wq_rec_import_result* out);
+int wq_records_import_device(wq_router* h, const wq_rec_row* d_rows, size_t n, uint64_t ops_seen,
+                             wq_rec_import_result* out);
 /* clamp_region_coord (world_region.rs:93-110) on the host; WQ_E_INVALID for size 0 or a NaN. */
 int wq_region_quantize(const double* coords, size_t n, uint16_t size, int64_t* out);
 /* clamp_table_size (world_region.rs:112-129) on the host. */

@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/wq_router.h"
 #include "wq_device.hpp"
 
 namespace wq {
@@ -214,6 +215,69 @@ __host__ __device__ __forceinline__ bool rec_kill(uint32_t* live, uint32_t row) 
 
 __host__ __device__ __forceinline__ bool rec_is_live(const uint32_t* live, uint32_t row) {
     return ((live[row >> 2] >> ((row & 3u) * 8u)) & 0xFFu) != 0;
+}
+
+// ---- vacuum and snapshots (wq_records_vacuum / _export / _import) ----
+
+// Row `src` of `from` becomes row `dst` of `to`: the nine fields and a set live byte (no kill runs
+// beside a move, and every lane writes another byte).
+__host__ __device__ __forceinline__ void rec_row_move(const RecRows& from, uint32_t src, const RecRows& to,
+                                                      uint32_t dst) {
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        to.k_hi[v][dst] = from.k_hi[v][src];
+        to.k_lo[v][dst] = from.k_lo[v][src];
+    }
+    to.uuid_hi[dst] = from.uuid_hi[src];
+    to.uuid_lo[dst] = from.uuid_lo[src];
+    to.ts[dst] = from.ts[src];
+    to.seq[dst] = from.seq[src];
+    to.handle[dst] = from.handle[src];
+    reinterpret_cast<uint8_t*>(to.live)[dst] = 1;
+}
+
+// A stored row as a snapshot carries it: the region key unpacked to the region's minimum corner.
+__host__ __device__ __forceinline__ wq_rec_row rec_row_export(const RecCfg& cfg, const RecRows& r, uint32_t row) {
+    wq_rec_row o;
+    uint32_t a[3];
+    unpack_key(r.k_lo[0][row], r.k_hi[0][row], &o.world, a);
+    o.handle = r.handle[row];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) o.region[d] = ((int64_t)a[d] - (int64_t)kAxisBias) * (int64_t)cfg.size[d];
+    o.uuid_hi = r.uuid_hi[row];
+    o.uuid_lo = r.uuid_lo[row];
+    o.ts_us = r.ts[row];
+    o.seq = r.seq[row];
+    return o;
+}
+
+// The packed keys of a snapshot row in a store of configuration cfg, false when the store does not
+// take it: a corner off the region grid, a region index outside [-2^23, 2^23), a world above
+// kMaxPackedWorld or a seq that is not below the snapshot's op counter. The keys come from the
+// integer indices, never from a position (clamp_region_coord sends -16.0 to region -32), and the
+// table from the region, never from the snapshot.
+__host__ __device__ __forceinline__ bool rec_row_import(const RecCfg& cfg, const wq_rec_row& in, uint64_t ops_seen,
+                                                        RecPacked* region, RecPacked* table) {
+    if (in.world > kMaxPackedWorld || in.seq >= ops_seen) return false;
+    int64_t ri[3], ti[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const int64_t s = (int64_t)cfg.size[d], c = in.region[d];
+        if (c % s != 0) return false;
+        ri[d] = c / s;
+        if (ri[d] < -(int64_t)kAxisBias || ri[d] >= (int64_t)kAxisBias) return false;
+        ti[d] = clamp_table_size_dev(c, (int64_t)cfg.table_size) / (int64_t)cfg.table_size;
+    }
+    return pack_key(in.world, ri[0], ri[1], ri[2], 1.0, &region->lo, &region->hi) &&
+           pack_key(in.world, ti[0], ti[1], ti[2], 1.0, &table->lo, &table->hi);
+}
+
+// Do elements t - 1 and t of view 0 (t >= 1) compare equal: the same (region key, uuid, ts, seq)?
+// Sorted, two such rows are neighbours; an import that holds a pair is refused.
+__host__ __device__ __forceinline__ bool rec_adjacent_equal(const RecRows& r, const uint32_t* __restrict__ view,
+                                                            uint32_t t) {
+    const RecKey a = rec_key<0>(r, view[t - 1]), b = rec_key<0>(r, view[t]);
+    return !rec_less(a, b) && !rec_less(b, a);
 }
 
 // ---- a read's ordinal space: the queries' ranges laid end to end, pre[i] = elements before query i

@@ -24,6 +24,13 @@
 //           emit      a wave per granule stores its winners as one contiguous run; one lane per query
 //                     derives its offset from the same prefix
 //           dedupe    each winner's (table, uuid) range in view 1: the rows older than it die
+//   vacuum  flag      one lane per stored row reads its live byte
+//           scan      each live row's new index, which is also the views' old-to-new map
+//           move      the live rows into fresh arrays (export: into the caller's wq_rec_row array)
+//           remap     both views through the map
+//   import  classify  one lane per snapshot row: validate, pack both keys from the integer indices
+//           scan / append / sort   as the apply, the sort keys read from the rows (seq is a pass too)
+//           check     no two neighbours of view 0 compare equal
 //
 // No lane, wave or block owns a region. Placement comes from prefix sums alone, so two calls give
 // the same bytes. An apply reads nothing back; a read reads its totals once, at its end.
@@ -42,6 +49,7 @@ struct RecCtl {
     uint32_t batch_m;  // creates of the apply in flight
     uint32_t n_long;   // its deletes whose range is longer than a lane walks
     uint64_t created, deleted_rows, rejected;  // since the store was opened (never zeroed)
+    uint32_t imp_rejected, imp_dup;            // an import's rejected rows and its pairs of equal rows
     uint64_t r_returned, r_deduped, r_rejected, r_scanned;
     uint32_t r_overflow;
     uint32_t r_cut;       // the walk stopped below the ranges' total
@@ -53,6 +61,7 @@ struct RecStore {
     RecCfg cfg;
     DevBuf k_hi[2], k_lo[2], uuid_hi, uuid_lo, ts, seq, handle, live, dead;
     uint64_t row_cap = 0;
+    uint64_t dead_extra = 0;  // the dead list holds row_cap + dead_extra entries (a vacuum keeps the undrained ones)
     DevBuf view[2][2];  // [view][buffer]: `cur` is in use, a merge or compaction writes the other
     int cur = 0;
     uint64_t view_cap = 0;
@@ -95,6 +104,8 @@ struct RecBatchKeys {
     uint32_t* hi[2];  // hi[0][i] == 0: op i has no key (rejected)
     uint64_t* lo[2];
 };
+
+uint32_t dead_cap_of(const RecStore* s) { return (uint32_t)std::min<uint64_t>(s->row_cap + s->dead_extra, 0xFFFFFFFFull); }
 
 // Kills a row once: the caller that found it live appends its handle to the dead list.
 __device__ __forceinline__ uint32_t kill_row(const RecRows& r, uint32_t row, RecCtl* ctl, uint32_t* dead,
@@ -153,10 +164,16 @@ __global__ __launch_bounds__(kBlock) void k_rec_append(const wq_rec_op* __restri
     reinterpret_cast<uint8_t*>(r.live)[row] = 1;  // no kill runs beside an append
 }
 
+// A snapshot row's seq; an op has none of its own (a batch ascends in it by construction).
+__host__ __device__ __forceinline__ uint64_t rec_op_seq(const wq_rec_op&) { return 0; }
+__host__ __device__ __forceinline__ uint64_t rec_op_seq(const wq_rec_row& r) { return r.seq; }
+
 // One key word of the batch's ops in the order `idx`: 0 ts_us (biased), 1 uuid_lo, 2 uuid_hi, 3 / 5
 // the low word of the region / table key, 4 / 6 its high word, above every key for an op that is
-// no accepted create (those sort to the end).
-__global__ __launch_bounds__(kBlock) void k_rec_sortkey(const wq_rec_op* __restrict__ ops,
+// no accepted create (those sort to the end). Op is wq_rec_op or, for an import, wq_rec_row, whose
+// word 7 is its seq (a snapshot's rows need not ascend in it).
+template <typename Op>
+__global__ __launch_bounds__(kBlock) void k_rec_sortkey(const Op* __restrict__ ops,
                                                         const uint32_t* __restrict__ idx, uint32_t n, int word,
                                                         RecBatchKeys b, const uint32_t* __restrict__ flag,
                                                         uint64_t* out) {
@@ -171,6 +188,7 @@ __global__ __launch_bounds__(kBlock) void k_rec_sortkey(const wq_rec_op* __restr
         case 3: k = b.lo[0][i]; break;
         case 4: k = flag[i] ? b.hi[0][i] : 1ull << 32; break;
         case 5: k = b.lo[1][i]; break;
+        case 7: k = rec_op_seq(ops[i]); break;
         default: k = flag[i] ? b.hi[1][i] : 1ull << 32; break;
     }
     out[j] = k;
@@ -286,6 +304,121 @@ __global__ __launch_bounds__(kBlock) void k_rec_cscatter(const uint32_t* __restr
 }
 
 __global__ void k_rec_cset(RecCtl* ctl) { ctl->n_view = ctl->n_view_next; }
+
+// ---- vacuum and export: a stable compaction of the rows by their live byte ----
+
+// One lane per stored row; the exclusive scan of the flags is each live row's new index and the
+// old-to-new map of the views.
+__global__ __launch_bounds__(kBlock) void k_rec_vflag(const uint32_t* __restrict__ live, uint64_t n_rows,
+                                                      uint32_t* flag) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t < n_rows) flag[t] = rec_is_live(live, (uint32_t)t) ? 1u : 0u;
+}
+
+// Coalesced loads, stores in monotone runs, into fresh arrays: map[t] <= t does not make a parallel
+// move in place safe.
+__global__ __launch_bounds__(kBlock) void k_rec_vmove(RecRows from, RecRows to, const uint32_t* __restrict__ map,
+                                                      uint64_t n_rows, uint64_t to_cap) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_rows || !rec_is_live(from.live, (uint32_t)t)) return;
+    const uint32_t p = map[t];
+    if (p < to_cap) rec_row_move(from, (uint32_t)t, to, p);
+}
+
+// The path's one gather: 4-byte reads over the map.
+__global__ __launch_bounds__(kBlock) void k_rec_vremap(const uint32_t* __restrict__ view,
+                                                       const uint32_t* __restrict__ map, uint64_t n, uint64_t n_rows,
+                                                       uint32_t* out) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t row = view[t];
+    if (row < n_rows) out[t] = map[row];
+}
+
+__global__ void k_rec_vset(RecCtl* ctl, uint32_t n_rows) { ctl->n_rows = n_rows; }
+
+// The move's walk storing one wq_rec_row per live row: four 16-byte stores.
+__global__ __launch_bounds__(kBlock) void k_rec_export(RecCfg cfg, RecRows r, const uint32_t* __restrict__ map,
+                                                       uint64_t n_rows, wq_rec_row* out, uint64_t capacity) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_rows || !rec_is_live(r.live, (uint32_t)t)) return;
+    const uint32_t p = map[t];
+    if (p >= capacity) return;
+    const wq_rec_row o = rec_row_export(cfg, r, (uint32_t)t);
+    auto lo = [](uint64_t v) { return (uint32_t)v; };
+    auto hi = [](uint64_t v) { return (uint32_t)(v >> 32); };
+    const uint64_t r0 = (uint64_t)o.region[0], r1 = (uint64_t)o.region[1], r2 = (uint64_t)o.region[2];
+    uint4* dst = reinterpret_cast<uint4*>(out + p);
+    dst[0] = make_uint4(o.world, o.handle, lo(r0), hi(r0));
+    dst[1] = make_uint4(lo(r1), hi(r1), lo(r2), hi(r2));
+    dst[2] = make_uint4(lo(o.uuid_hi), hi(o.uuid_hi), lo(o.uuid_lo), hi(o.uuid_lo));
+    dst[3] = make_uint4(lo((uint64_t)o.ts_us), hi((uint64_t)o.ts_us), lo(o.seq), hi(o.seq));
+}
+
+// ---- import: the bulk build of both views from a snapshot ----
+
+__global__ __launch_bounds__(kBlock) void k_rec_iclassify(RecCfg cfg, const wq_rec_row* __restrict__ rows, uint32_t n,
+                                                          uint64_t ops_seen, RecBatchKeys b, uint32_t* flag,
+                                                          RecCtl* ctl) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    bool rejected = false;
+    if (i < n) {
+        RecPacked rk{0, 0}, tk{0, 0};
+        const bool ok = rec_row_import(cfg, rows[i], ops_seen, &rk, &tk);
+        rejected = !ok;
+        b.hi[0][i] = ok ? rk.hi : 0u;
+        b.lo[0][i] = rk.lo;
+        b.hi[1][i] = ok ? tk.hi : 0u;
+        b.lo[1][i] = tk.lo;
+        flag[i] = ok ? 1u : 0u;
+    }
+    const uint64_t w = __ballot(rejected);
+    if ((threadIdx.x & 63u) == 0 && w) atomicAdd(&ctl->imp_rejected, (uint32_t)__popcll(w));
+}
+
+// The accepted rows in the given order, each under its own seq (the store is empty: row = pos).
+__global__ __launch_bounds__(kBlock) void k_rec_iappend(const wq_rec_row* __restrict__ rows, uint32_t n,
+                                                        RecBatchKeys b, const uint32_t* __restrict__ flag,
+                                                        const uint32_t* __restrict__ pos, RecRows r, uint64_t row_cap,
+                                                        RecCtl* ctl) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (i == n - 1) ctl->batch_m = pos[i] + flag[i];
+    if (!flag[i]) return;
+    const uint32_t row = pos[i];
+    if (row >= row_cap) return;  // never: the host sized the rows for the whole snapshot
+    const wq_rec_row in = rows[i];
+    for (int v = 0; v < 2; ++v) {
+        r.k_hi[v][row] = b.hi[v][i];
+        r.k_lo[v][row] = b.lo[v][i];
+    }
+    r.uuid_hi[row] = in.uuid_hi;
+    r.uuid_lo[row] = in.uuid_lo;
+    r.ts[row] = in.ts_us;
+    r.seq[row] = in.seq;
+    r.handle[row] = in.handle;
+    reinterpret_cast<uint8_t*>(r.live)[row] = 1;
+}
+
+// The sorted snapshot indices become row indices, straight into the (empty) views.
+__global__ __launch_bounds__(kBlock) void k_rec_iviews(const uint32_t* __restrict__ s0,
+                                                       const uint32_t* __restrict__ s1, uint32_t n,
+                                                       const uint32_t* __restrict__ pos, const RecCtl* ctl,
+                                                       uint32_t* v0, uint32_t* v1, uint64_t view_cap) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n || j >= ctl->batch_m || j >= view_cap) return;
+    v0[j] = pos[s0[j]];
+    v1[j] = pos[s1[j]];
+}
+
+// No two neighbours of view 0 may compare equal: a ballot per wave, one atomic per wave.
+__global__ __launch_bounds__(kBlock) void k_rec_icheck(RecRows r, const uint32_t* __restrict__ v0, uint32_t n,
+                                                       RecCtl* ctl) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    const bool dup = t >= 1 && t < n && t < ctl->batch_m && rec_adjacent_equal(r, v0, t);
+    const uint64_t w = __ballot(dup);
+    if ((threadIdx.x & 63u) == 0 && w) atomicAdd(&ctl->imp_dup, (uint32_t)__popcll(w));
+}
 
 // ---- read ----
 
@@ -484,7 +617,8 @@ int ensure_rows(wq_router* h, RecStore* s, uint64_t need) {
         if (int rc = grow_keep(h, *b, cap * 8, have * 8)) return rc;
     if (int rc = grow_keep(h, s->handle, cap * 4, have * 4)) return rc;
     if (int rc = grow_keep(h, s->live, cap, (have + 3) & ~3ull)) return rc;
-    if (int rc = grow_keep(h, s->dead, cap * 4, have * 4)) return rc;  // every row dies at most once
+    // every row dies at most once
+    if (int rc = grow_keep(h, s->dead, (cap + s->dead_extra) * 4, (have + s->dead_extra) * 4)) return rc;
     s->row_cap = cap;
     return WQ_OK;
 }
@@ -500,9 +634,10 @@ int ensure_views(wq_router* h, RecStore* s, uint64_t need) {
     return WQ_OK;
 }
 
-int sort_pass(wq_router* h, RecStore* s, const wq_rec_op* d_ops, uint32_t n, int word, int end_bit, RecBatchKeys b,
+template <typename Op>
+int sort_pass(wq_router* h, RecStore* s, const Op* d_ops, uint32_t n, int word, int end_bit, RecBatchKeys b,
               const uint32_t* in, uint32_t* out) {
-    hipLaunchKernelGGL(k_rec_sortkey, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, d_ops, in, n, word, b,
+    hipLaunchKernelGGL(k_rec_sortkey<Op>, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, d_ops, in, n, word, b,
                        s->b_flag.as<uint32_t>(), s->b_key[0].as<uint64_t>());
     WQ_HIP(h, hipGetLastError());
     return sort_pairs<uint64_t>(h, s->b_key[0].as<uint64_t>(), s->b_key[1].as<uint64_t>(), in, out, n, end_bit);
@@ -579,7 +714,7 @@ int records_apply_device(wq_router* h, const wq_rec_op* d_ops, size_t n_ops) {
     s->view_ub += n;
     s->ops_seen += n;
     uint32_t* dead = s->dead.as<uint32_t>();
-    const uint32_t dead_cap = (uint32_t)std::min<uint64_t>(s->row_cap, 0xFFFFFFFFull);
+    const uint32_t dead_cap = dead_cap_of(s);
     hipLaunchKernelGGL(k_rec_delete, grid, block, 0, st, d_ops, n, b, r, s->view[0][nx].as<uint32_t>(), seq0, ctl, dead,
                        dead_cap, s->b_long.as<uint32_t>());
     const unsigned grid_l = std::min<unsigned>(kRecMaxBlocks, (n + kRecWaves - 1) / kRecWaves);
@@ -677,7 +812,7 @@ int records_read_device(wq_router* h, size_t n_q, const uint32_t* d_world, const
         WQ_HIP(h, hipGetLastError());
         if (n && (flags & WQ_RECORD_READ_DEDUPE)) {
             hipLaunchKernelGGL(k_rec_dedupe, dim3(grid_g), block, 0, st, r, v0, v1, pre, q_lo, q_len, n, lim, fl, ctl,
-                               s->dead.as<uint32_t>(), (uint32_t)std::min<uint64_t>(s->row_cap, 0xFFFFFFFFull));
+                               s->dead.as<uint32_t>(), dead_cap_of(s));
             WQ_HIP(h, hipGetLastError());
         }
         return read_ctl(h, s);
@@ -694,6 +829,192 @@ int records_read_device(wq_router* h, size_t n_q, const uint32_t* d_world, const
     s->tot_deduped += c.r_deduped;
     s->tot_rejected_queries += c.r_rejected;
     if (out) *out = wq_rec_read_result{c.r_returned, c.r_deduped, c.r_rejected, c.r_scanned, c.r_overflow, 0};
+    return WQ_OK;
+}
+
+// ---- vacuum, export, import ----
+
+// The buffers a vacuum reallocates: the row arrays, the dead list and the views.
+uint64_t store_bytes(const RecStore* s) {
+    uint64_t b = 0;
+    for (int v = 0; v < 2; ++v) b += s->k_hi[v].bytes + s->k_lo[v].bytes + s->view[v][0].bytes + s->view[v][1].bytes;
+    for (const DevBuf* d : {&s->uuid_hi, &s->uuid_lo, &s->ts, &s->seq, &s->handle, &s->live, &s->dead}) b += d->bytes;
+    return b;
+}
+
+// Flag and scan over the stored rows: s->b_pos[t] is live row t's index among the live rows.
+int rows_map(wq_router* h, RecStore* s, uint64_t n_rows) {
+    WQ_ALLOC(h, s->b_flag, n_rows * 4);
+    WQ_ALLOC(h, s->b_pos, n_rows * 4);
+    hipLaunchKernelGGL(k_rec_vflag, dim3(grid_for(n_rows)), dim3(kBlock), 0, h->stream, s->live.as<uint32_t>(), n_rows,
+                       s->b_flag.as<uint32_t>());
+    WQ_HIP(h, hipGetLastError());
+    return scan_u32(h, s->b_flag.as<uint32_t>(), s->b_pos.as<uint32_t>(), n_rows, false);
+}
+
+int records_vacuum(wq_router* h, wq_rec_vacuum_result* out) {
+    RecStore* s = h->rec;
+    hipStream_t st = h->stream;
+    if (int rc = records_compact(h, s)) return rc;  // both views hold live rows only
+    if (int rc = read_ctl(h, s)) return rc;         // the one read: the live count sizes the new arrays
+    const uint64_t S = s->pinned->n_rows, L = s->pinned->live, P = s->pinned->n_dead;
+    wq_rec_vacuum_result res{S, S, store_bytes(s), store_bytes(s)};
+    if (out) *out = res;
+    if (S == L) return WQ_OK;  // nothing dead (an empty store too): nothing moves, nothing is allocated
+    if (int rc = rows_map(h, s, S)) return rc;
+    const uint64_t cap = (std::max<uint64_t>(L, 1024) + 3) & ~3ull;
+    // fresh arrays, all of them before anything moves: a failed allocation leaves the store as it was
+    RecStore f;
+    hipError_t e = hipSuccess;
+    auto get = [&](DevBuf& b, uint64_t bytes) {
+        if (e == hipSuccess) e = b.ensure(bytes);
+    };
+    for (int v = 0; v < 2; ++v) {
+        get(f.k_hi[v], cap * 4);
+        get(f.k_lo[v], cap * 8);
+        get(f.view[v][0], cap * 4);
+        get(f.view[v][1], cap * 4);
+    }
+    for (DevBuf* b : {&f.uuid_hi, &f.uuid_lo, &f.ts, &f.seq}) get(*b, cap * 8);
+    get(f.handle, cap * 4);
+    get(f.live, cap);
+    get(f.dead, (cap + P) * 4);  // the pending entries plus one per row
+    auto swap_all = [&]() {  // f's arrays <-> the store's
+        for (int v = 0; v < 2; ++v) {
+            std::swap(f.k_hi[v], s->k_hi[v]);
+            std::swap(f.k_lo[v], s->k_lo[v]);
+            std::swap(f.view[v][0], s->view[v][0]);
+            std::swap(f.view[v][1], s->view[v][1]);
+        }
+        for (DevBuf RecStore::*m : {&RecStore::uuid_hi, &RecStore::uuid_lo, &RecStore::ts, &RecStore::seq,
+                                    &RecStore::handle, &RecStore::live, &RecStore::dead})
+            std::swap(f.*m, s->*m);
+    };
+    auto drop = [&]() {
+        for (int v = 0; v < 2; ++v)
+            for (DevBuf* b : {&f.k_hi[v], &f.k_lo[v], &f.view[v][0], &f.view[v][1]}) b->release();
+        for (DevBuf* b : {&f.uuid_hi, &f.uuid_lo, &f.ts, &f.seq, &f.handle, &f.live, &f.dead}) b->release();
+    };
+    if (e != hipSuccess) {
+        drop();
+        return set_error(h, WQ_E_OOM, "record store vacuum", e);
+    }
+    const uint32_t* map = s->b_pos.as<uint32_t>();
+    hipLaunchKernelGGL(k_rec_vmove, dim3(grid_for(S)), dim3(kBlock), 0, st, rows_of(s), rows_of(&f), map, S, cap);
+    if (L) {
+        for (int v = 0; v < 2; ++v)
+            hipLaunchKernelGGL(k_rec_vremap, dim3(grid_for(L)), dim3(kBlock), 0, st, s->view[v][s->cur].as<uint32_t>(), map,
+                               L, S, f.view[v][0].as<uint32_t>());
+    }
+    hipLaunchKernelGGL(k_rec_vset, dim3(1), dim3(1), 0, st, s->ctl.as<RecCtl>(), (uint32_t)L);
+    e = hipGetLastError();
+    if (e == hipSuccess && P) e = hipMemcpyAsync(f.dead.p, s->dead.p, P * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {  // (the counter may already say L: the handle is in error either way)
+        drop();
+        return set_error(h, WQ_E_HIP, "record store vacuum", e);
+    }
+    swap_all();
+    drop();  // the old arrays
+    s->cur = 0;
+    s->row_cap = s->view_cap = cap;
+    s->dead_extra = P;
+    s->rows_ub = s->view_ub = L;
+    res.rows_after = L;
+    res.bytes_after = store_bytes(s);
+    if (out) *out = res;
+    return WQ_OK;
+}
+
+// The live rows as wq_rec_row into d_out (device memory); the count is read first.
+int records_export_device(wq_router* h, wq_rec_row* d_out, size_t capacity, size_t* n, uint64_t* ops_seen) {
+    RecStore* s = h->rec;
+    if (int rc = read_ctl(h, s)) return rc;
+    const uint64_t S = s->pinned->n_rows, L = s->pinned->live;
+    *n = (size_t)L;
+    if (ops_seen) *ops_seen = s->ops_seen;
+    if (L > capacity) return set_error(h, WQ_E_CAPACITY, "snapshot capacity too small (required size in *n)");
+    if (!L) return WQ_OK;
+    if (int rc = rows_map(h, s, S)) return rc;
+    hipLaunchKernelGGL(k_rec_export, dim3(grid_for(S)), dim3(kBlock), 0, h->stream, s->cfg, rows_of(s),
+                       s->b_pos.as<uint32_t>(), S, d_out, (uint64_t)capacity);
+    WQ_HIP(h, hipGetLastError());
+    WQ_HIP(h, hipStreamSynchronize(h->stream));
+    return WQ_OK;
+}
+
+// The bulk build from a snapshot on the device: classify, scan, append, sort, check; one read-back.
+int records_import_device(wq_router* h, const wq_rec_row* d_rows, size_t n_rows, uint64_t ops_seen,
+                          wq_rec_import_result* out) {
+    RecStore* s = h->rec;
+    hipStream_t st = h->stream;
+    if (out) *out = wq_rec_import_result{0, 0};
+    if (int rc = read_ctl(h, s)) return rc;
+    if (s->ops_seen != 0 || s->pinned->n_rows != 0)
+        return set_error(h, WQ_E_INVALID, "an import needs a store that has received no op");
+    if (n_rows >= 0xFFFFFFFFull) return set_error(h, WQ_E_CAPACITY, "the record store holds fewer than 2^32 - 1 rows");
+    if (n_rows == 0) {
+        s->ops_seen = ops_seen;
+        return WQ_OK;
+    }
+    const uint32_t n = (uint32_t)n_rows;
+    if (int rc = ensure_rows(h, s, n)) return rc;
+    if (int rc = ensure_views(h, s, n)) return rc;
+    for (int v = 0; v < 2; ++v) {
+        WQ_ALLOC(h, s->b_hi[v], (size_t)n * 4);
+        WQ_ALLOC(h, s->b_lo[v], (size_t)n * 8);
+        WQ_ALLOC(h, s->b_key[v], (size_t)n * 8);
+        WQ_ALLOC(h, s->b_sorted[v], (size_t)n * 4);
+    }
+    for (DevBuf* b : {&s->b_flag, &s->b_pos, &s->b_i[0], &s->b_i[1], &s->b_i[2]}) WQ_ALLOC(h, *b, (size_t)n * 4);
+    RecCtl* ctl = s->ctl.as<RecCtl>();
+    WQ_HIP(h, hipMemsetAsync(&ctl->imp_rejected, 0, 2 * sizeof(uint32_t), st));
+    WQ_HIP(h, hipMemsetAsync(&ctl->batch_m, 0, 2 * sizeof(uint32_t), st));
+    const RecRows r = rows_of(s);
+    const RecBatchKeys b{{s->b_hi[0].as<uint32_t>(), s->b_hi[1].as<uint32_t>()},
+                         {s->b_lo[0].as<uint64_t>(), s->b_lo[1].as<uint64_t>()}};
+    uint32_t* flag = s->b_flag.as<uint32_t>();
+    uint32_t* pos = s->b_pos.as<uint32_t>();
+    const dim3 grid(grid_for(n)), block(kBlock);
+    hipLaunchKernelGGL(k_rec_iclassify, grid, block, 0, st, s->cfg, d_rows, n, ops_seen, b, flag, ctl);
+    WQ_HIP(h, hipGetLastError());
+    if (int rc = scan_u32(h, flag, pos, n, false)) return rc;
+    hipLaunchKernelGGL(k_rec_iappend, grid, block, 0, st, d_rows, n, b, flag, pos, r, s->row_cap, ctl);
+    WQ_HIP(h, hipGetLastError());
+    // both views' order by stable passes from the last key word up; a snapshot's rows need not ascend
+    // in seq, so seq is a pass too
+    uint32_t* i0 = s->b_i[0].as<uint32_t>();
+    uint32_t* i1 = s->b_i[1].as<uint32_t>();
+    uint32_t* i2 = s->b_i[2].as<uint32_t>();
+    uint32_t* s0 = s->b_sorted[0].as<uint32_t>();
+    uint32_t* s1 = s->b_sorted[1].as<uint32_t>();
+    hipLaunchKernelGGL(k_iota, grid, block, 0, st, i0, (uint64_t)n);
+    WQ_HIP(h, hipGetLastError());
+    if (int rc = sort_pass(h, s, d_rows, n, 7, 64, b, i0, i1)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 0, 64, b, i1, i0)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 1, 64, b, i0, i1)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 2, 64, b, i1, i0)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 3, 64, b, i0, i1)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 4, 33, b, i1, s0)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 5, 64, b, i0, i2)) return rc;
+    if (int rc = sort_pass(h, s, d_rows, n, 6, 33, b, i2, s1)) return rc;
+    uint32_t* v0 = s->view[0][s->cur].as<uint32_t>();
+    uint32_t* v1 = s->view[1][s->cur].as<uint32_t>();
+    hipLaunchKernelGGL(k_rec_iviews, grid, block, 0, st, s0, s1, n, pos, ctl, v0, v1, s->view_cap);
+    hipLaunchKernelGGL(k_rec_icheck, grid, block, 0, st, r, v0, n, ctl);
+    hipLaunchKernelGGL(k_rec_commit, dim3(1), dim3(1), 0, st, ctl);
+    WQ_HIP(h, hipGetLastError());
+    if (int rc = read_ctl(h, s)) return rc;  // the one read-back of the build
+    const uint64_t imported = s->pinned->n_rows, rejected = s->pinned->imp_rejected;
+    if (s->pinned->imp_dup) {
+        WQ_HIP(h, hipMemsetAsync(ctl, 0, sizeof(RecCtl), st));
+        WQ_HIP(h, hipStreamSynchronize(st));
+        s->rows_ub = s->view_ub = 0;
+        s->dirty = false;
+        return set_error(h, WQ_E_INVALID, "the snapshot holds two rows with the same region, uuid, time and seq");
+    }
+    s->ops_seen = ops_seen;
+    if (out) *out = wq_rec_import_result{imported, rejected};
     return WQ_OK;
 }
 
@@ -878,6 +1199,57 @@ int wq_records_totals(wq_router* h, wq_rec_totals* out) {
     const RecCtl& c = *s->pinned;
     *out = wq_rec_totals{c.created, c.deleted_rows, s->tot_deduped, c.rejected, s->tot_rejected_queries};
     return WQ_OK;
+}
+
+int wq_records_vacuum(wq_router* h, wq_rec_vacuum_result* out) {
+    if (int rc = records_check(h)) return rc;
+    WQ_HIP(h, hipSetDevice(h->device));
+    return records_vacuum(h, out);
+}
+
+int wq_records_export_device(wq_router* h, wq_rec_row* d_out, size_t capacity, size_t* n, uint64_t* ops_seen) {
+    if (int rc = records_check(h)) return rc;
+    if (!n || (capacity && !d_out)) return set_error(h, WQ_E_INVALID, "null array");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return set_error(h, WQ_E_INVALID, "the snapshot array is 16-byte aligned");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return records_export_device(h, d_out, capacity, n, ops_seen);
+}
+
+int wq_records_export(wq_router* h, wq_rec_row* out, size_t capacity, size_t* n, uint64_t* ops_seen) {
+    if (int rc = records_check(h)) return rc;
+    if (!n || (capacity && !out)) return set_error(h, WQ_E_INVALID, "null array");
+    WQ_HIP(h, hipSetDevice(h->device));
+    RecStore* s = h->rec;
+    if (int rc = read_ctl(h, s)) return rc;
+    const size_t k = (size_t)s->pinned->live;
+    if (k <= capacity) WQ_ALLOC(h, s->out, k * sizeof(wq_rec_row));  // the staging fits the rows exactly
+    if (int rc = records_export_device(h, s->out.as<wq_rec_row>(), k <= capacity ? k : 0, n, ops_seen)) return rc;
+    if (k) {
+        WQ_HIP(h, hipMemcpyAsync(out, s->out.p, k * sizeof(wq_rec_row), hipMemcpyDeviceToHost, h->stream));
+        WQ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return WQ_OK;
+}
+
+int wq_records_import_device(wq_router* h, const wq_rec_row* d_rows, size_t n, uint64_t ops_seen,
+                             wq_rec_import_result* out) {
+    if (int rc = records_check(h)) return rc;
+    if (n && !d_rows) return set_error(h, WQ_E_INVALID, "null snapshot");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return records_import_device(h, d_rows, n, ops_seen, out);
+}
+
+int wq_records_import(wq_router* h, const wq_rec_row* rows, size_t n, uint64_t ops_seen, wq_rec_import_result* out) {
+    if (int rc = records_check(h)) return rc;
+    if (n && !rows) return set_error(h, WQ_E_INVALID, "null snapshot");
+    if (n >= 0xFFFFFFFFull) return set_error(h, WQ_E_CAPACITY, "the record store holds fewer than 2^32 - 1 rows");
+    WQ_HIP(h, hipSetDevice(h->device));
+    RecStore* s = h->rec;
+    if (n) {
+        WQ_ALLOC(h, s->in, n * sizeof(wq_rec_row));
+        WQ_HIP(h, hipMemcpyAsync(s->in.p, rows, n * sizeof(wq_rec_row), hipMemcpyHostToDevice, h->stream));
+    }
+    return records_import_device(h, s->in.as<wq_rec_row>(), n, ops_seen, out);
 }
 
 int wq_region_quantize(const double* coords, size_t n, uint16_t size, int64_t* out) {

@@ -29,6 +29,19 @@ REC_OP_DTYPE = np.dtype([("kind", np.uint32), ("world", np.uint32), ("pos", np.f
                          ("handle", np.uint32), ("reserved", np.uint32)])  # struct wq_rec_op
 assert REC_OP_DTYPE.itemsize == 64
 
+REC_ROW_DTYPE = np.dtype([("world", np.uint32), ("handle", np.uint32), ("region", np.int64, (3,)),
+                          ("uuid_hi", np.uint64), ("uuid_lo", np.uint64), ("ts_us", np.int64),
+                          ("seq", np.uint64)])  # struct wq_rec_row: one stored row of a snapshot
+assert REC_ROW_DTYPE.itemsize == 64
+
+
+class RecVacuumResult(ctypes.Structure):  # struct wq_rec_vacuum_result
+    _fields_ = [(f, ctypes.c_uint64) for f in ("rows_before", "rows_after", "bytes_before", "bytes_after")]
+
+
+class RecImportResult(ctypes.Structure):  # struct wq_rec_import_result
+    _fields_ = [("imported", ctypes.c_uint64), ("rejected", ctypes.c_uint64)]
+
 
 class RecApplyResult(ctypes.Structure):  # struct wq_rec_apply_result
     _fields_ = [("created", ctypes.c_uint64), ("deleted_rows", ctypes.c_uint64), ("rejected", ctypes.c_uint64),
@@ -260,6 +273,61 @@ class RecordStoreRef:
         """Counts since the store was made (wq_records_totals)."""
         return dict(self.totals_)
 
+    # -- vacuum and snapshots --
+    def _index(self):
+        """The three lookup lists from the rows (ascending row index, as appends leave them)."""
+        self.by_region, self.by_table_uuid, self.by_region_uuid = {}, {}, {}
+        for i, row in enumerate(self.rows):
+            self.by_region.setdefault((row["world"], row["region"]), []).append(i)
+            self.by_table_uuid.setdefault((row["world"], row["table"], row["uuid"]), []).append(i)
+            self.by_region_uuid.setdefault((row["world"], row["region"], row["uuid"]), []).append(i)
+        self.__dict__.pop("_swept", None)
+
+    def vacuum(self) -> dict:
+        """wq_records_vacuum: the dead rows go, the live ones keep their order, seq, ts and handle.
+        Nothing a later call returns changes but `rows_stored`; the undrained dead list stays."""
+        before = len(self.rows)
+        if before != self.live:
+            self.rows = [row for row in self.rows if row["live"]]
+            self._index()
+        return {"rows_before": before, "rows_after": len(self.rows)}
+
+    def export_rows(self) -> tuple:
+        """wq_records_export: (the live rows in row order as REC_ROW_DTYPE, ops_seen). Changes nothing."""
+        live = [row for row in self.rows if row["live"]]
+        out = np.zeros(len(live), dtype=REC_ROW_DTYPE)
+        for i, row in enumerate(live):
+            out[i] = (row["world"], row["handle"], row["region"], row["uuid"][0], row["uuid"][1], row["ts"], row["seq"])
+        return out, self.ops_seen
+
+    def import_rows(self, rows, ops_seen: int) -> dict:
+        """wq_records_import into a store that has received no op (else ValueError). A row whose
+        corner is off this store's region grid, whose region index or world is not packable or whose
+        seq is not below `ops_seen` is rejected and counted; two accepted rows with the same (world,
+        region, uuid, ts, seq) refuse the import (ValueError, the store stays empty). The table is
+        this store's, computed from the region."""
+        if self.ops_seen != 0 or self.rows:
+            raise ValueError("an import needs a store that has received no op")
+        accepted, seen, rejected = [], set(), 0
+        for r in rows:
+            world, seq = int(r["world"]), int(r["seq"])
+            reg = tuple(int(c) for c in r["region"])
+            if (world > MAX_PACKED_WORLD or seq >= ops_seen or any(c % s for c, s in zip(reg, self.sizes))
+                    or not all(-AXIS_BIAS <= c // s < AXIS_BIAS for c, s in zip(reg, self.sizes))):
+                rejected += 1
+                continue
+            uuid = (int(r["uuid_hi"]), int(r["uuid_lo"]))
+            key = (world, reg, uuid, int(r["ts_us"]), seq)
+            if key in seen:
+                raise ValueError("the snapshot holds two rows with the same region, uuid, time and seq")
+            seen.add(key)
+            accepted.append({"world": world, "region": reg, "table": self.table(reg), "uuid": uuid,
+                             "ts": int(r["ts_us"]), "seq": seq, "handle": int(r["handle"]), "live": True})
+        self.rows = accepted
+        self._index()
+        self.live, self.ops_seen = len(accepted), int(ops_seen)
+        return {"imported": len(accepted), "rejected": rejected}
+
 
 def make_ops(kind, world, pos, uuid_hi, uuid_lo, ts_us=0, handle=0) -> np.ndarray:
     """REC_OP_DTYPE array from broadcastable columns (pos: [n, 3])."""
@@ -364,6 +432,48 @@ class GpuRecordStore:
         self.router._check(self.lib.wq_records_totals(self.h, ctypes.byref(t)))
         return {f: int(getattr(t, f)) for f, _ in RecTotals._fields_}
 
+    def vacuum(self) -> dict:
+        """wq_records_vacuum: rows and bytes (row arrays, dead list, views) before and after."""
+        res = RecVacuumResult()
+        self.router._check(self.lib.wq_records_vacuum(self.h, ctypes.byref(res)))
+        return {f: int(getattr(res, f)) for f, _ in RecVacuumResult._fields_}
+
+    def export_device(self, rows_ptr: int, capacity: int) -> tuple:
+        """wq_records_export_device into device memory with room for `capacity` rows: (the live
+        count, ops_seen). A capacity below the count writes nothing and raises WQError (WQ_E_CAPACITY);
+        a null pointer with capacity 0 asks for the count."""
+        n, ops = ctypes.c_size_t(), ctypes.c_uint64()
+        rc = self.lib.wq_records_export_device(self.h, rows_ptr or None, capacity, ctypes.byref(n), ctypes.byref(ops))
+        if not (rc == abi.WQ_E_CAPACITY and not capacity):
+            self.router._check(rc)
+        return n.value, ops.value
+
+    def export_rows(self) -> tuple:
+        """wq_records_export: (the live rows in row order as REC_ROW_DTYPE, ops_seen)."""
+        n, ops = ctypes.c_size_t(), ctypes.c_uint64()
+        rc = self.lib.wq_records_export(self.h, None, 0, ctypes.byref(n), ctypes.byref(ops))
+        if rc not in (0, abi.WQ_E_CAPACITY):
+            self.router._check(rc)
+        out = np.zeros(n.value, dtype=REC_ROW_DTYPE)
+        if n.value:
+            self.router._check(self.lib.wq_records_export(self.h, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                          ctypes.byref(n), ctypes.byref(ops)))
+        return out, ops.value
+
+    def import_device(self, rows_ptr: int, n: int, ops_seen: int) -> dict:
+        """wq_records_import_device: n wq_rec_row in device memory into this (unused) store."""
+        res = RecImportResult()
+        self.router._check(self.lib.wq_records_import_device(self.h, rows_ptr or None, n, ops_seen, ctypes.byref(res)))
+        return {"imported": int(res.imported), "rejected": int(res.rejected)}
+
+    def import_rows(self, rows, ops_seen: int) -> dict:
+        """wq_records_import of REC_ROW_DTYPE rows (WQError: a used store or a duplicate row)."""
+        rows = np.ascontiguousarray(rows, dtype=REC_ROW_DTYPE)
+        res = RecImportResult()
+        self.router._check(self.lib.wq_records_import(
+            self.h, rows.ctypes.data_as(ctypes.c_void_p) if len(rows) else None, len(rows), ops_seen, ctypes.byref(res)))
+        return {"imported": int(res.imported), "rejected": int(res.rejected)}
+
 
 def region_quantize(lib, coords, size: int) -> np.ndarray:
     """wq_region_quantize (host)."""
@@ -404,10 +514,15 @@ class RecordProcessor:
     `RecordStoreRef`). The payload of a record (its data, flex and exact position) stays here, in a
     slab indexed by the `handle` the store keeps; slots of rows the store killed are freed from its
     dead list. Events are dicts: {"instruction", "world_name", "sender_uuid", "parameter",
-    "position", "records"}, a record {"uuid": (hi, lo), "world_name", "position", "data", "flex"}."""
+    "position", "records"}, a record {"uuid": (hi, lo), "world_name", "position", "data", "flex"}.
+    With `vacuum_dead_fraction` set, the store is vacuumed after a `process` call once more than that
+    share of its stored rows is dead; the replies are the same either way."""
 
-    def __init__(self, store, worlds: WorldIds | None = None, dedupe: bool = True):
+    def __init__(self, store, worlds: WorldIds | None = None, dedupe: bool = True,
+                 vacuum_dead_fraction: float | None = None):
         self.store = store
+        self.vacuum_dead_fraction = vacuum_dead_fraction
+        self.vacuums = 0
         self.worlds = worlds if worlds is not None else WorldIds()
         self.dedupe = dedupe
         self.slab: list = []
@@ -512,6 +627,11 @@ class RecordProcessor:
                 ops.extend(self._ops(CREATE if ins == "RecordCreate" else DELETE, ev, now_us))
         flush_ops()
         flush_reads()
+        if self.vacuum_dead_fraction is not None:
+            live, stored, _ = self.store.stats()
+            if stored and 1.0 - live / stored > self.vacuum_dead_fraction:
+                self.store.vacuum()
+                self.vacuums += 1
         return replies
 
     def _free_dead(self):

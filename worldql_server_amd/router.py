@@ -89,6 +89,11 @@ def load_library(build_if_missing: bool = True):
         "wq_records_drain_dead": ([vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_records_stats": ([vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3, i32),
         "wq_records_totals": ([vp, vp], i32),
+        "wq_records_vacuum": ([vp, vp], i32),
+        "wq_records_export": ([vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)], i32),
+        "wq_records_export_device": ([vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)], i32),
+        "wq_records_import": ([vp, vp, sz, ctypes.c_uint64, vp], i32),
+        "wq_records_import_device": ([vp, vp, sz, ctypes.c_uint64, vp], i32),
         "wq_region_quantize": ([vp, sz, u16, vp], i32),
         "wq_table_quantize": ([vp, sz, u32, vp], i32),
         "wq_is_subscribed": ([vp, sz, vp, vp, i32, vp, vp], i32),
