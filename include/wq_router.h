@@ -273,6 +273,49 @@ int wq_follow_last_ops(wq_router* h, const wq_op** d_ops, size_t* n);
  * `capacity` (nothing copied). */
 int wq_follow_read_ops(wq_router* h, wq_op* out, size_t capacity, size_t* n);
 
+/* The follow state itself, so a restarted server goes on where the old one stopped (a restored table
+ * with an empty follow state would subscribe every peer's whole neighbourhood again and never
+ * unsubscribe the cubes it has left since).
+ * wq_follow_state_read: world[n] and pos[n x 3] for the n peers the state covers (the largest n a
+ * follow call or a load was given since the last reset). A peer that is not followed reads
+ * WQ_WORLD_INVALID and +0.0 three times. *n is always the full count; peers at index >= capacity are
+ * not written and the call returns WQ_E_CAPACITY; null arrays with capacity 0 ask for the count.
+ * wq_follow_state_load: installs world[n], pos[n x 3] as the state and emits no op; n_followed
+ * counts from it. Only while no peer is followed (WQ_E_INVALID otherwise, as wq_follow_set_reach).
+ * The reach is not part of the state: set it first. Both are synchronous; a multi-GPU handle keeps
+ * the state on devices[0]. */
+int wq_follow_state_read(wq_router* h, uint32_t* world, double* pos, size_t capacity, size_t* n);
+int wq_follow_state_load(wq_router* h, const uint32_t* world, const double* pos, size_t n);
+
+/* ---- table snapshots: the subscriptions as a canonical op stream ----
+ * An extension: the reference keeps its WorldMap in memory only and cannot list it.
+ * Every live (world, cube, peer) that passes the filter becomes one wq_op: kind WQ_OP_SUBSCRIBE,
+ * key_is_raw = 1, u.key = the CubeArea exactly as the table holds it, pad_ zero. Import is
+ * wq_apply_ops[_device] of those rows into an empty handle (wq_sharded_apply_ops with the same
+ * rows on every shard; the ordinary apply on a multi-GPU handle): there is no import entry point.
+ * Rows ascend by (world as u32, key x, y, z as i64, peer as u32), so two handles holding the same
+ * subscription set export the same bytes whatever their history (rebuilds, in-place batches,
+ * relocated lists, wq_remove_peers, truncated hash bits, record slack, header layout, one GPU or
+ * several). A cube whose list has been emptied yields nothing.
+ *   - The pending incremental batch is folded in first: an export right after wq_apply_ops_device
+ *     sees that batch.
+ *   - *n is always the full row count. Rows at index >= capacity are not written and the call then
+ *     returns WQ_E_CAPACITY; a null array with capacity 0 asks for the count.
+ *   - Both forms are synchronous (they wait for the totals). The _device form leaves the rows in
+ *     device memory (8-byte aligned) on the handle's device, devices[0] for a multi-GPU handle.
+ *   - Multi-GPU: the replicate layout exports replica 0; the cube-hash layout exports every shard
+ *     and merges on devices[0]. A single handle with an exchange attached (wq_shard_attach_*)
+ *     exports the buckets it owns, without communication.
+ * The filter: `peers` is a HOST array in both forms. */
+typedef struct wq_export_filter {
+    uint32_t world;        /* WQ_WORLD_INVALID: every world */
+    uint32_t n_peers;
+    const uint32_t* peers; /* NULL: every peer; else exactly these ids (any order, duplicates and ids
+                              nobody holds allowed; n_peers may be 0) */
+} wq_export_filter;        /* a NULL filter = everything */
+int wq_table_export(wq_router* h, const wq_export_filter* f, wq_op* out, size_t capacity, size_t* n);
+int wq_table_export_device(wq_router* h, const wq_export_filter* f, wq_op* d_out, size_t capacity, size_t* n);
+
 /* ---- tick shape: the caller's expected recipients per message (e.g. its previous tick's
  * n_pairs / M; no reference counterpart — the Rust loop routes one message at a time,
  * thread.rs:125-146). At >= WQ_HEAVY_FANOUT the tick runs as count / scan / emit launches, whose

@@ -47,6 +47,10 @@ DIFF_OVERFLOW_LEFT = 2
 DIFF_ERROR_ROWS = 1        # wq_diff_counters.error bit 0: a row was cut to the part inside bounds
 
 
+class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
+    _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]
+
+
 def make_op(world: int, peer: int, kind: int, pos=None, key=None) -> np.void:
     """One wq_op record; give `pos` (Vector3, quantised) or `key` (raw CubeArea)."""
     o = np.zeros((), dtype=OP_DTYPE)

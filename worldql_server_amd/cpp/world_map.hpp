@@ -82,6 +82,9 @@ class AreaMap {
     bool remove_subscription(uint32_t peer, const CubeArea& c) { return mutate(peer, WQ_OP_UNSUBSCRIBE, c); }
     bool remove_subscription(uint32_t peer, const Vector3& v) { return mutate(peer, WQ_OP_UNSUBSCRIBE, v); }
     bool remove_peer(uint32_t peer);
+    // The cubes `peer` is subscribed to in this world, ascending by (x, y, z): one filtered export
+    // (the reference would scan every cube, area_map.rs:113).
+    std::vector<CubeArea> subscriptions_of(uint32_t peer) const;
 
    private:
     friend class WorldMap;
@@ -138,6 +141,24 @@ class WorldMap {
 
     // batch paths (the throughput API)
     void apply_ops(const std::vector<wq_op>& ops) { check(wq_apply_ops(h_, ops.data(), ops.size())); }
+    // The table as a canonical op stream (wq_table_export): one SUBSCRIBE op with a raw key per live
+    // (world, cube, peer), ascending by (world, key, peer); filter == nullptr exports everything.
+    // apply_ops of the rows on an empty map of the same cube size rebuilds the table; the world ids
+    // in the rows are this map's (world_names() lists the names in id order for the restart).
+    std::vector<wq_op> export_ops(const wq_export_filter* filter = nullptr) const {
+        size_t n = 0;
+        int rc = wq_table_export(h_, filter, nullptr, 0, &n);
+        if (rc && rc != WQ_E_CAPACITY) check(rc);
+        std::vector<wq_op> rows(n);
+        check(wq_table_export(h_, filter, rows.data(), rows.size(), &n));
+        rows.resize(n);
+        return rows;
+    }
+    std::vector<std::string> world_names() const {
+        std::vector<std::string> names(maps_.size());
+        for (auto& kv : maps_) names[kv.second->world_id()] = kv.first;
+        return names;
+    }
     struct Routed {
         std::vector<uint32_t> offsets, peers;
     };
@@ -214,6 +235,13 @@ inline bool AreaMap::remove_peer(uint32_t peer) {  // area_map.rs:124-135
     op.kind = WQ_OP_REMOVE_PEER;
     wm_->check(wq_apply_ops(wm_->handle(), &op, 1));
     return was;
+}
+
+inline std::vector<CubeArea> AreaMap::subscriptions_of(uint32_t peer) const {
+    const wq_export_filter f{id_, 1, &peer};
+    std::vector<CubeArea> out;
+    for (const wq_op& op : wm_->export_ops(&f)) out.push_back(CubeArea{op.u.key[0], op.u.key[1], op.u.key[2]});
+    return out;
 }
 
 inline std::vector<uint32_t> AreaMap::get_subscribed_peers(const CubeArea& c) const {

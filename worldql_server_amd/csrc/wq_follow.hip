@@ -219,6 +219,7 @@ int follow_device(wq_router* h, const uint32_t* d_world, const double* d_pos, si
     if (out) *out = wq_follow_result{0, 0, h->fol_n};
     if (n == 0) return WQ_OK;
     if (int rc = grow_state(h, n)) return rc;
+    h->fol_len = std::max<uint64_t>(h->fol_len, n);
     WQ_ALLOC(h, h->fol_cnt, n * 4);
     WQ_ALLOC(h, h->fol_off, n * 4);
     WQ_ALLOC(h, h->fol_mask, n * 8);
@@ -288,6 +289,47 @@ int wq_follow_reset(wq_router* h) {
     WQ_HIP(h, hipSetDevice(h->device));
     if (h->fol_cap) WQ_HIP(h, hipMemsetAsync(h->fol_world.p, 0xFF, h->fol_cap * 4, h->stream));
     h->fol_n = 0;
+    h->fol_len = 0;
+    return WQ_OK;
+}
+
+int wq_follow_state_read(wq_router* h, uint32_t* world, double* pos, size_t capacity, size_t* n) {
+    if (!h || !n || (capacity && (!world || !pos))) return WQ_E_INVALID;
+    *n = h->fol_len;
+    const size_t m = std::min<size_t>(capacity, h->fol_len);
+    if (m) {
+        WQ_HIP(h, hipSetDevice(h->device));
+        WQ_HIP(h, hipMemcpyAsync(world, h->fol_world.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+        WQ_HIP(h, hipMemcpyAsync(pos, h->fol_pos.p, m * 24, hipMemcpyDeviceToHost, h->stream));
+        WQ_HIP(h, hipStreamSynchronize(h->stream));
+        // the position words of a peer that is not followed hold whatever it was last followed at
+        for (size_t i = 0; i < m; ++i)
+            if (world[i] == WQ_WORLD_INVALID) pos[3 * i] = pos[3 * i + 1] = pos[3 * i + 2] = 0.0;
+    }
+    if (h->fol_len > capacity)
+        return set_error(h, WQ_E_CAPACITY, "follow state capacity too small (required size in *n)");
+    return WQ_OK;
+}
+
+int wq_follow_state_load(wq_router* h, const uint32_t* world, const double* pos, size_t n) {
+    if (!h || (n && (!world || !pos))) return WQ_E_INVALID;
+    if (n >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "peer ids are below 2^32 - 1");
+    if (h->fol_n) return set_error(h, WQ_E_INVALID, "a follow state can only be loaded while no peer is followed");
+    WQ_HIP(h, hipSetDevice(h->device));
+    // a pending batch may still be re-applied from the op buffer of the follow call that made it
+    if (!h->multi)
+        if (int rc = table_resolve(h, true)) return rc;
+    if (int rc = grow_state(h, n)) return rc;
+    if (h->fol_cap) WQ_HIP(h, hipMemsetAsync(h->fol_world.p, 0xFF, h->fol_cap * 4, h->stream));
+    uint64_t followed = 0;
+    if (n) {
+        WQ_HIP(h, hipMemcpyAsync(h->fol_world.p, world, n * 4, hipMemcpyHostToDevice, h->stream));
+        WQ_HIP(h, hipMemcpyAsync(h->fol_pos.p, pos, n * 24, hipMemcpyHostToDevice, h->stream));
+        for (size_t i = 0; i < n; ++i) followed += world[i] != WQ_WORLD_INVALID;
+    }
+    WQ_HIP(h, hipStreamSynchronize(h->stream));
+    h->fol_n = followed;
+    h->fol_len = n;
     return WQ_OK;
 }
 

@@ -153,6 +153,15 @@ struct ProfileEvents {
     bool enabled = false;
 };
 
+// Scratch of the table export (wq_table_export.hip), grow-only: per table slot the live flag and its
+// prefix; per live cube the sort words, count and table slot, then count, slot and row base in
+// canonical order; per granule of 64 rows the filter's flag word, count and prefix; the peer bitmap;
+// the totals; the host form's (and a multi-GPU merge's) device image of the rows.
+struct ExportWs {
+    DevBuf flag, pos, keys, cnt, src, ocnt, osrc, base, gword, gcnt, gbase, bits, tot, stage, merge;
+    void* pinned = nullptr;
+};
+
 struct ShardCtx;  // shard_ctx.hpp: the exchange a sharded tick uses, and its workspace
 struct MultiCtx;  // wq_multi.hip: a handle over G GPUs (wq_router_create_multi)
 struct RecStore;  // wq_records.hip: the record store (wq_records_open)
@@ -227,6 +236,7 @@ struct wq_router {
     uint64_t fol_cap = 0;    // peers the state covers
     uint64_t fol_n = 0;      // peers followed now
     uint64_t fol_n_ops = 0;  // ops of the latest call
+    uint64_t fol_len = 0;    // peers wq_follow_state_read reports: the largest n a call or a load covered
     uint32_t fol_reach = 1;
     // interest diff (wq_csr_diff.hip): per row the clamped lengths of both sides and their prefix,
     // per granule the counts and their prefix, the granules' flag words, and two error slots (each
@@ -234,6 +244,7 @@ struct wq_router {
     wq::DevBuf diff_len, diff_pre, diff_cnt, diff_base, diff_flags, diff_err;
     uint64_t diff_calls = 0;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
+    wq::ExportWs exp;             // wq_table_export*
 };
 
 namespace wq {
@@ -331,6 +342,10 @@ int launch_csr_diff(wq_router* h, size_t n_rows, const uint32_t* d_old_offsets, 
 void csr_diff_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
+// wq_table_export.hip: frees the export's scratch.
+void export_release(wq_router* h);
+// wq_multi.hip: the sub-handles of a multi-GPU handle (the export walks them itself)
+uint32_t multi_subs(wq_router* h, wq_router*** sub, const int** dev, int* mode);
 // wq_multi.hip: the multi-GPU handle's side of the entry points (h->multi != nullptr)
 int multi_merge_any(wq_router* h);
 int multi_apply_ops(wq_router* h, const wq_op* ops, size_t n);

@@ -457,6 +457,14 @@ int multi_apply_ops_device(wq_router* h, const wq_op* d_ops, size_t n) {
     return run_all(h, [&](uint32_t g) { return apply_staged(h, g, m.part.as<wq_op>() + off[g], c[g]); });
 }
 
+uint32_t multi_subs(wq_router* h, wq_router*** sub, const int** dev, int* mode) {
+    MultiCtx& m = *h->multi;
+    *sub = m.sub.data();
+    *dev = m.dev.data();
+    *mode = m.mode;
+    return m.G;
+}
+
 int multi_remove_peers(wq_router* h, const uint32_t* peers, size_t n) {
     h->multi->any_dirty = true;
     return run_all(h, [&](uint32_t g) { return wq_remove_peers(h->multi->sub[g], peers, n); });

@@ -126,6 +126,7 @@ int wq_router_destroy(wq_router* h) {
     follow_release(h);
     csr_diff_release(h);
     records_release(h);
+    export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
         for (auto e : *v) (void)hipEventDestroy(e);
     DevBuf* bufs[] = {&h->st.h, &h->st.w, &h->st.kx, &h->st.ky, &h->st.kz, &h->st.p,

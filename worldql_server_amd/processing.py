@@ -72,6 +72,16 @@ class SubscriptionProcessor:
         self.world_map = world_map
         self.broadcast = broadcast
 
+    def snapshot(self, follow_reach: int = 1) -> dict:
+        """The processor's whole state (WorldMap.snapshot): it keeps nothing between ticks itself."""
+        return self.world_map.snapshot(follow_reach)
+
+    @classmethod
+    def restore(cls, snap: dict, broadcast: Optional[Callable[[Message, Recipients], None]] = None,
+                device: int = 0, router=None) -> "SubscriptionProcessor":
+        """A processor that goes on exactly where the snapshot's one stopped."""
+        return cls(WorldMap.restore(snap, device, router), broadcast)
+
     def process_tick(self, events: Sequence[Message]) -> List[Optional[Recipients]]:
         """For every event: the recipients of a Local/GlobalMessage (a list of peers, or a
         PeerMapBroadcast for "@global"), or None when nothing is broadcast — a table event, a

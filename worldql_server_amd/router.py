@@ -122,6 +122,10 @@ def load_library(build_if_missing: bool = True):
         "wq_follow_peers_device": ([vp, vp, vp, sz, ctypes.POINTER(FollowResult)], i32),
         "wq_follow_last_ops": ([vp, ctypes.POINTER(vp), ctypes.POINTER(sz)], i32),
         "wq_follow_read_ops": ([vp, vp, sz, ctypes.POINTER(sz)], i32),
+        "wq_follow_state_read": ([vp, vp, vp, sz, ctypes.POINTER(sz)], i32),
+        "wq_follow_state_load": ([vp, vp, vp, sz], i32),
+        "wq_table_export": ([vp, ctypes.POINTER(abi.ExportFilter), vp, sz, ctypes.POINTER(sz)], i32),
+        "wq_table_export_device": ([vp, ctypes.POINTER(abi.ExportFilter), vp, sz, ctypes.POINTER(sz)], i32),
         "wq_set_fanout_hint": ([vp, ctypes.c_double], i32),
         "wq_debug_route_shape": ([vp, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
         "wq_route_health": ([vp, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
@@ -594,6 +598,74 @@ class Router:
         got = ctypes.c_size_t()
         self._check(self.lib.wq_follow_read_ops(self.h, _p(out) if n else None, n, ctypes.byref(got)))
         return out[: got.value]
+
+    def follow_state(self):
+        """(world[n], pos[n x 3]) of the peers the follow state covers (wq_follow_state_read); a peer
+        that is not followed reads abi.WORLD_INVALID and zeros."""
+        n = ctypes.c_size_t()
+        rc = self.lib.wq_follow_state_read(self.h, None, None, 0, ctypes.byref(n))
+        if rc not in (0, abi.WQ_E_CAPACITY):
+            self._check(rc)
+        w = np.zeros(n.value, np.uint32)
+        p = np.zeros((n.value, 3), np.float64)
+        if n.value:
+            self._check(self.lib.wq_follow_state_read(self.h, _p(w), _p(p), n.value, ctypes.byref(n)))
+        return w, p
+
+    def follow_state_load(self, world, pos) -> None:
+        """Installs a follow state (wq_follow_state_load): no op is emitted; only while no peer is
+        followed. Set the reach first."""
+        w = np.ascontiguousarray(world, dtype=np.uint32)
+        p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        if len(p) != len(w):
+            raise ValueError("world and pos must cover the same peers")
+        self._check(self.lib.wq_follow_state_load(self.h, _p(w), _p(p), len(w)))
+
+    # ---- table snapshots (include/wq_router.h; host definition: snapshot.py) ----
+    @staticmethod
+    def _export_filter(world, peers):
+        """(ctypes pointer or None, the array it points into)."""
+        if world is None and peers is None:
+            return None, None
+        ids = None if peers is None else np.ascontiguousarray(peers, dtype=np.uint32).reshape(-1)
+        if ids is not None and len(ids) == 0:
+            ids = np.zeros(1, np.uint32)[:0]
+        f = abi.ExportFilter(abi.WORLD_INVALID if world is None else int(world), 0 if ids is None else len(ids), None)
+        if ids is not None:  # (a zero-length list still needs a non-null pointer: null = every peer)
+            f.peers = ids.ctypes.data
+        return ctypes.pointer(f), (ids, f)
+
+    def export_table(self, world=None, peers=None, capacity: int | None = None, out=None) -> np.ndarray:
+        """Every live (world, cube, peer) as one SUBSCRIBE op with a raw key, in canonical order
+        (wq_table_export): `world` None = every world, `peers` None = every peer. With `capacity`
+        only that many rows are asked for: the call then raises WQError(WQ_E_CAPACITY) when the
+        table holds more. `out` (abi.OP_DTYPE, e.g. a PinnedArray's array) receives the rows."""
+        fp, keep = self._export_filter(world, peers)
+        n = ctypes.c_size_t()
+        if capacity is None and out is None:
+            rc = self.lib.wq_table_export(self.h, fp, None, 0, ctypes.byref(n))
+            if rc not in (0, abi.WQ_E_CAPACITY):
+                self._check(rc)
+            capacity = n.value
+        if out is None:
+            out = np.zeros(capacity, dtype=abi.OP_DTYPE)
+        elif capacity is None:
+            capacity = len(out)
+        self._check(self.lib.wq_table_export(self.h, fp, _p(out) if capacity else None, capacity, ctypes.byref(n)))
+        del keep
+        return out[: n.value]
+
+    def export_table_device(self, ptr: int, capacity: int, world=None, peers=None):
+        """The same into device memory on the handle's device (wq_table_export_device). Returns
+        (rc, n): n is the full row count, rc WQ_E_CAPACITY when it exceeds `capacity` (the first
+        `capacity` rows are written); other errors raise."""
+        fp, keep = self._export_filter(world, peers)
+        n = ctypes.c_size_t()
+        rc = self.lib.wq_table_export_device(self.h, fp, ptr or None, capacity, ctypes.byref(n))
+        del keep
+        if rc not in (0, abi.WQ_E_CAPACITY):
+            self._check(rc)
+        return rc, n.value
 
     def set_fanout_hint(self, pairs_per_message: float) -> None:
         """Expected recipients per message (e.g. the previous tick's P / M): >= 16 selects the

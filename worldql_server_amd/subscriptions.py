@@ -101,6 +101,20 @@ class PeerIds:
     def peers(self, pids) -> list:
         return [self._peers[int(p)] for p in pids]
 
+    def snapshot(self) -> dict:
+        """The id map as plain data: id -> peer (None: free), and the free list in pop order."""
+        return {"peers": list(self._peers), "free": list(self._free)}
+
+    @classmethod
+    def restore(cls, snap: dict) -> "PeerIds":
+        self = cls()
+        self._peers = list(snap["peers"])
+        self._free = list(snap["free"])
+        self._ids = {peer: pid for pid, peer in enumerate(self._peers) if peer is not None}
+        if sorted(self._free) != [pid for pid, peer in enumerate(self._peers) if peer is None]:
+            raise ValueError("peer id snapshot: the free list does not match the unused ids")
+        return self
+
 
 class WorldMap:
     """world_map.rs:10-62. One GPU table holds every world; a world "exists" once `get_mut`
@@ -122,6 +136,31 @@ class WorldMap:
             am = AreaMap(self, world_name, self.worlds.intern(world_name))
             self._maps[world_name] = am
         return am
+
+    def snapshot(self, follow_reach: int = 1) -> dict:
+        """Everything a restart needs: the table's rows and follow state (snapshot.take) and what the
+        GPU never sees and the rows' ids mean nothing without — the world names in id order and the
+        peer id map with its free list. The follow reach is the caller's (the handle has no getter)."""
+        from . import snapshot as _snapshot
+        return {"table": _snapshot.take(self.router, follow_reach),
+                "worlds": [self.worlds.name(i) for i in range(len(self.worlds))],
+                "maps": list(self._maps),
+                "peer_ids": self.peer_ids.snapshot()}
+
+    @classmethod
+    def restore(cls, snap: dict, device: int = 0, router: Optional[Router] = None) -> "WorldMap":
+        """A WorldMap holding exactly what `snap` held, on a fresh table (or the given empty Router
+        of the same cube size): same world ids, same peer ids, same free list."""
+        from . import snapshot as _snapshot
+        table = snap["table"]
+        self = cls(table.cube_size, device, router)
+        _snapshot.restore(self.router, table)
+        for name in snap["worlds"]:
+            self.worlds.intern(name)
+        for name in snap["maps"]:
+            self.get_mut(name)
+        self.peer_ids = PeerIds.restore(snap["peer_ids"])
+        return self
 
     def remove_peer(self, uuid: Hashable) -> bool:  # world_map.rs:41-61
         pid = self.peer_ids.lookup(uuid)
@@ -189,6 +228,15 @@ class AreaMap:
         was = self.is_peer_subscribed(uuid, cube)
         self._r.apply_ops(np.array([self._op(uuid, cube, abi.OP_UNSUBSCRIBE)], abi.OP_DTYPE))
         return was
+
+    def subscriptions_of(self, uuid: Hashable) -> list:
+        """The cubes `uuid` is subscribed to in this world, ascending (the reference would scan every
+        cube, area_map.rs:113; here it is one filtered export)."""
+        pid = self._wm.peer_ids.lookup(uuid)
+        if pid is None:
+            return []
+        rows = self._r.export_table(world=self.world_id, peers=[pid])
+        return [CubeArea(*k) for k in rows["key"].tolist()]
 
     def remove_peer(self, uuid: Hashable) -> bool:  # :124-135
         was = self.is_peer_subscribed_any(uuid)
