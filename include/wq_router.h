@@ -196,7 +196,18 @@ int wq_route_tick(wq_router* h, const double* pos, const int64_t* keys, const ui
                   uint32_t* peers, uint32_t* msgs, size_t capacity, size_t* n_pairs);
 /* Asynchronous form on device pointers; nothing is read back. counters (device pointer to a
  * wq_route_counters) receives P, F and the overflow / error flags (also kept sticky for
- * wq_route_health). Pairs beyond `capacity` are not written. */
+ * wq_route_health). Pairs beyond `capacity` are not written.
+ * A tick whose P exceeds `capacity` still completes (tests/test_gpu_truncation.py):
+ *   - d_offsets[0 .. n_msgs] are complete: d_offsets[n_msgs] = P, not clipped to `capacity`;
+ *   - d_peers / d_msgs hold exactly the first `capacity` pairs of the full result (the last message
+ *     kept may be cut inside its recipients); nothing at index >= capacity is written, and with
+ *     P < capacity nothing at index >= P either;
+ *   - the counters carry the full P and F, overflow = 1, error = 0; wq_route_tick returns
+ *     WQ_E_CAPACITY with *n_pairs = P after copying the same offsets and prefix;
+ *   - capacity = 0 asks for offsets and counters only (d_peers and d_msgs are not touched);
+ *   - wq_csr_diff* reads such a tick as it is, with new_capacity = `capacity`.
+ * d_peers and d_msgs are expected 16-byte aligned, as every hipMalloc result is: the kernels store
+ * 16-byte quads at pair indices that are multiples of four. */
 int wq_route_tick_device(wq_router* h, const double* d_pos, const int64_t* d_keys,
                          const uint32_t* d_world, const uint32_t* d_sender, const uint8_t* d_repl,
                          size_t n_msgs, uint32_t* d_offsets, uint32_t* d_peers, uint32_t* d_msgs,
