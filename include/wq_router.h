@@ -206,6 +206,22 @@ int wq_route_tick(wq_router* h, const double* pos, const int64_t* keys, const ui
  *     WQ_E_CAPACITY with *n_pairs = P after copying the same offsets and prefix;
  *   - capacity = 0 asks for offsets and counters only (d_peers and d_msgs are not touched);
  *   - wq_csr_diff* reads such a tick as it is, with new_capacity = `capacity`.
+ * A tick whose P exceeds 2^32 - 1, the most that u32 offsets address, is reported, never mistaken for a
+ * smaller one — in every tick shape, with or without the radius filter, wq_route_global* included
+ * (tests/test_gpu_pair_limit.py):
+ *   - counters.n_pairs is the exact P for P < 2^40 (beyond that some value >= 2^40 - 1: the
+ *     single-launch tick carries 40 bits of it from block to block); n_candidates is the exact F;
+ *   - counters.error has bit 2 and overflow = (P > capacity), i.e. 1 (capacities count as at most
+ *     2^32 - 1); wq_route_health reports bit 2 once, then (0, 0);
+ *   - d_offsets[0 .. n_msgs] are written and nothing behind them; their values are unspecified (they
+ *     are the true offsets modulo 2^32);
+ *   - the contents of d_peers / d_msgs are unspecified; nothing at index >= capacity is written, and
+ *     with capacity 0 they are not touched;
+ *   - wq_route_tick and wq_route_global return WQ_E_CAPACITY with *n_pairs = P and leave offsets,
+ *     peers and msgs untouched; a multi-GPU handle (wq_router_create_multi*) returns WQ_E_CAPACITY
+ *     from the host and the device form, with *n_pairs / counters.n_pairs >= 2^32;
+ *   - the next tick on the handle is exact.
+ * P = 2^32 - 1 is an ordinary tick: offsets[n_msgs] = 0xFFFFFFFF, error 0.
  * d_peers and d_msgs are expected 16-byte aligned, as every hipMalloc result is: the kernels store
  * 16-byte quads at pair indices that are multiples of four. */
 int wq_route_tick_device(wq_router* h, const double* d_pos, const int64_t* d_keys,
@@ -810,6 +826,12 @@ int wq_debug_set_route_config(wq_router* h, int cfg);
  * count is done (0 = the default; 1 = one chunk). Applies to ticks of >= 2 chunks of at most 8,192
  * count tiles each. Results are identical for every value. */
 int wq_debug_set_route_chunks(wq_router* h, int chunks);
+/* ---- test hook: the handle's route-call counter (single-GPU handles). The single-launch tick tags
+ * its look-back granules with this counter modulo 2^22 - 1, plus one, and zeroes them each time the
+ * tags wrap; moving the counter lets a test place two long ticks one tag period apart without
+ * running the four million ticks between them. Results are identical for every value. */
+int wq_debug_set_route_calls(wq_router* h, uint64_t calls);
+int wq_debug_route_calls(wq_router* h, uint64_t* calls);
 /* The tick shape the next default-config tick takes (heavy_fanout = count / scan / emit) and
  * whether it is still chosen automatically (no hint set, or reset by a negative hint). */
 int wq_debug_route_shape(wq_router* h, int* heavy_fanout, int* fanout_auto);

@@ -27,6 +27,10 @@ REPL_ONLY_SELF = 2
 
 WORLD_INVALID = 0xFFFFFFFF
 
+MAX_PAIRS = 0xFFFFFFFF             # pairs per tick: the CSR offsets are u32 (error bit 2, WQ_E_CAPACITY beyond)
+ROUTE_ERROR_PAIR_LIMIT = 2         # wq_route_counters.error bit 2
+TICK_TAG_PERIOD = (1 << 22) - 1    # route calls after which the single-launch tick's granule tags repeat
+
 # struct wq_op: 40 bytes; `key` aliases `pos` (union).
 OP_DTYPE = np.dtype({
     "names": ["world", "peer", "kind", "key_is_raw", "pos", "key"],

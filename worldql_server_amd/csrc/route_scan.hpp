@@ -146,11 +146,23 @@ static __global__ __launch_bounds__(kScanThreads) void tile_scan_kernel(TileScan
 // partial sums into the call's counters, P from the last tile, the overflow / error flags.
 static __global__ __launch_bounds__(kBlock) void tile_finish_kernel(TileScanParams p) {
     __shared__ uint64_t s_F[kWaves];
+    __shared__ uint64_t s_E[kWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t F = 0;
     for (uint32_t i = blockIdx.x * kBlock + tid; i < p.n_tiles; i += gridDim.x * kBlock) F += p.tile_F[i];
     F = wave_sum_u64(F);
-    if (lane == 0) s_F[wave] = F;
+    // P: block 0 sums every tile's total itself, in 64 bits. The scanned prefixes are u32 and wrap as
+    // the CSR offsets do, so tile_prefix[last] + tile_total[last] is P mod 2^32: a tick past the limit
+    // would report a small P, no error bit, and overflow only by chance.
+    uint64_t E = 0;
+    if (blockIdx.x == 0) {
+        for (uint32_t i = tid; i < p.n_tiles; i += kBlock) E += p.tile_total[i];
+        E = wave_sum_u64(E);
+    }
+    if (lane == 0) {
+        s_F[wave] = F;
+        s_E[wave] = E;
+    }
     lds_barrier();
     if (tid == 0) {
         uint64_t Fb = 0;
@@ -159,8 +171,9 @@ static __global__ __launch_bounds__(kBlock) void tile_finish_kernel(TileScanPara
         atomicAdd(reinterpret_cast<unsigned long long*>(&p.cnt->n_candidates), (unsigned long long)Fb);
     }
     if (blockIdx.x == 0 && tid == 0) {
-        const uint32_t last = p.n_tiles - 1;
-        const uint64_t P = (uint64_t)p.tile_prefix[last] + p.tile_total[last];  // no u32 wrap below 2^32
+        uint64_t P = 0;
+#pragma unroll
+        for (int u = 0; u < kWaves; ++u) P += s_E[u];
         p.offsets[p.M] = (uint32_t)P;
         p.cnt->n_pairs = P;
         flag_route(p.cnt, p.health, P > 0xFFFFFFFFull ? 2u : 0u, P > p.capacity ? 1u : 0u);
@@ -427,8 +440,9 @@ inline int launch_scan_u32(wq_router* h, const uint32_t* in, uint32_t* out, uint
 constexpr uint32_t kScanOneBlockMax = 8192;  // tiles: up to here the one-block scan is the faster
 
 // The tick's tile scan (n_tiles >= 1): one block for a few thousand tiles (C2: 3,907),
-// rocPRIM + tile_finish_kernel beyond. P must fit the u32 offsets either way (error bit 2 if not);
-// a tick of > 2^32 pairs wraps the prefix, which the error bit already reports. With sp.async_end,
+// the multi-block scan beyond (WQ_SCAN_MULTI=0: rocPRIM + tile_finish_kernel). P must fit the u32
+// offsets (error bit 2 if not): every path sums P itself in 64 bits, apart from the u32 prefixes, which
+// wrap as the offsets do in a tick of > 2^32 - 1 pairs (tests/test_gpu_pair_limit.py). With sp.async_end,
 // *async_done says whether the scan took the asynchronous tick's end (the one-block scan only).
 inline int launch_tile_scan(wq_router* h, const TileScanParams& sp, bool* async_done = nullptr,
                             bool* out_done = nullptr) {

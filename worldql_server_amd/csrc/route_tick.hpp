@@ -33,7 +33,7 @@ struct TickParams {
     EmitOut out;        // peers == nullptr: offsets only
     uint64_t* look;     // [gridDim.x] look-back granules
     uint64_t* fgran;    // [gridDim.x] tagged per-block candidate counts (summed by the last block)
-    uint32_t tag;       // this call's tag, 1 .. 2^30-1, differs from the previous call's
+    uint32_t tag;       // this call's tag, 1 .. 2^22-1, differs from the previous call's
     wq_route_counters* cnt;
     wq_route_counters* cnt_next;
     uint32_t* health;   // sticky {error, overflow} words (flag_route)
@@ -48,15 +48,24 @@ constexpr uint32_t kErrSpin = 4u;
 constexpr uint32_t kSpinLimit = 1u << 21;  // x s_sleep(2) ~ 0.1 s, far beyond any tick
 constexpr uint32_t kFlagA = 1u, kFlagP = 2u;
 
-// granule: [tag:30][flag:2][value:32]
-__device__ __forceinline__ uint64_t granule(uint32_t tag, uint32_t flag, uint32_t v) {
-    return ((uint64_t)((tag << 2) | flag) << 32) | v;
+// granule: [tag:22][flag:2][value:40]. The value carries block totals and inclusive prefixes of the
+// pair count: 40 bits, so that a tick past the u32 offsets' 2^32 - 1 pairs still knows its exact P
+// (below 2^40; the value saturates there) and reports error bit 2 instead of a wrapped, legal-looking
+// P. 22 tag bits: launch_route zeroes the granules each time the tags wrap (kTickTagPeriod).
+constexpr uint32_t kGranValueBits = 40;
+constexpr uint64_t kGranValueMax = (1ull << kGranValueBits) - 1ull;
+constexpr uint32_t kTickTagPeriod = (1u << (62 - kGranValueBits)) - 1u;  // tags 1 .. 2^22 - 1
+__device__ __forceinline__ uint64_t granule(uint32_t tag, uint32_t flag, uint64_t v) {
+    return ((uint64_t)((tag << 2) | flag) << kGranValueBits) | (v < kGranValueMax ? v : kGranValueMax);
 }
+__device__ __forceinline__ uint32_t granule_tag(uint64_t g) { return (uint32_t)(g >> (kGranValueBits + 2)); }
+__device__ __forceinline__ uint32_t granule_flag(uint64_t g) { return (uint32_t)(g >> kGranValueBits) & 3u; }
+__device__ __forceinline__ uint64_t granule_value(uint64_t g) { return g & kGranValueMax; }
 
 __device__ __forceinline__ uint64_t poll_granule(const uint64_t* g, uint32_t tag, bool* gave_up) {
     for (uint32_t it = 0;; ++it) {
         const uint64_t v = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((uint32_t)(v >> 34) == tag) return v;
+        if (granule_tag(v) == tag) return v;
         if (it >= kSpinLimit) {
             *gave_up = true;
             return granule(tag, kFlagP, 0);
@@ -73,10 +82,10 @@ __device__ __forceinline__ uint64_t look_back(const uint64_t* look, uint32_t b, 
         const int64_t idx = hi - lane;  // lane 0 = the nearest block
         uint64_t v = 0;
         if (idx >= 0) v = poll_granule(look + idx, tag, gave_up);
-        const uint32_t flag = (uint32_t)(v >> 32) & 3u;
+        const uint32_t flag = granule_flag(v);
         const uint64_t pm = __ballot(idx >= 0 && flag == kFlagP);
         const int first = pm ? __builtin_ctzll(pm) : 64;  // nearest inclusive prefix
-        const uint64_t x = (lane <= first && idx >= 0) ? (uint32_t)v : 0u;
+        const uint64_t x = (lane <= first && idx >= 0) ? granule_value(v) : 0ull;
         acc += wave_sum_u64(x);
         if (pm) break;
     }
@@ -238,8 +247,7 @@ __global__ __launch_bounds__(kBlock) void tick_kernel(TickParams p) {
         uint64_t Fb = 0;
 #pragma unroll
         for (int u = 0; u < kWaves; ++u) Fb += sm.wave_u64[u];
-        __hip_atomic_store(p.fgran + b, granule(p.tag, kFlagA, Fb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)Fb),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p.fgran + b, granule(p.tag, kFlagA, Fb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(p.look + b, granule(p.tag, b == 0 ? kFlagP : kFlagA, T), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -257,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void tick_kernel(TickParams p) {
         if (b > 0) {
             pre = look_back(p.look, b, p.tag, &gave_up);
             if (lane == 0) {
-                __hip_atomic_store(p.look + b, granule(p.tag, kFlagP, (uint32_t)(pre + T)), __ATOMIC_RELAXED,
+                __hip_atomic_store(p.look + b, granule(p.tag, kFlagP, pre + T), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             }
         }
@@ -275,7 +283,7 @@ __global__ __launch_bounds__(kBlock) void tick_kernel(TickParams p) {
     if (b == NB - 1) {  // ... and sums every block's candidate count, all four waves polling
         bool gave_up = false;
         uint64_t F = 0;
-        for (uint32_t k = tid; k < NB; k += kBlock) F += (uint32_t)poll_granule(p.fgran + k, p.tag, &gave_up);
+        for (uint32_t k = tid; k < NB; k += kBlock) F += granule_value(poll_granule(p.fgran + k, p.tag, &gave_up));
         F = wave_sum_u64(F);
         const bool any_gave_up = __any(gave_up);  // the whole wave votes, not lane 0 alone
         if (lane == 0) {

@@ -66,6 +66,7 @@ struct GlobalParams {
     uint32_t* msgs;
     uint64_t capacity;
     wq_route_counters* cnt_next;
+    const wq_route_counters* cnt;  // this call's counters, final after the tile scan
 };
 
 __global__ __launch_bounds__(kBlock) void global_count_kernel(GlobalParams p) {
@@ -143,6 +144,10 @@ __global__ __launch_bounds__(kBlock) void global_offsets_kernel(GlobalParams p) 
 // offset is <= k (binary search over the offsets, L2-resident), and is copied from that world's
 // contiguous any-key range — so one message to a 50k-peer world spreads over the whole GPU.
 __global__ __launch_bounds__(kBlock) void global_copy_kernel(GlobalParams p) {
+    // a tick past 2^32 - 1 pairs (error bit 2, set by the tile scan before this launch): its offsets
+    // wrapped, so the search below would land on a wrong message and read `any` far outside its
+    // range. The contents of peers / msgs are unspecified for such a tick: nothing is written.
+    if (p.cnt->error & 2u) return;
     const uint32_t P = p.offsets[p.M];
     const uint64_t lim = P < p.capacity ? P : p.capacity;
     for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < lim; k += (uint64_t)gridDim.x * kBlock) {
@@ -192,6 +197,7 @@ int launch_route_global(wq_router* h, const uint32_t* d_world, const uint32_t* d
     gp.msgs = d_msgs;
     gp.capacity = capacity;
     gp.cnt_next = nxt;
+    gp.cnt = cur;
     hipLaunchKernelGGL(global_count_kernel, dim3(n_tiles), dim3(kBlock), 0, s, gp);
     WQ_HIP(h, hipGetLastError());
     TileScanParams sp;

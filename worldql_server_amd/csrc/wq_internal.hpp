@@ -128,6 +128,7 @@ struct RouteWs {
     uint64_t sgran_zeroed = 0;  // granules zeroed so far (a fresh one never matches a tag)
     uint64_t scan_calls = 0;    // multi-block scans so far (their tags)
     uint64_t agg_zeroed = 0;
+    uint64_t agg_epoch = 0;  // calls / kTickTagPeriod when agg was last zeroed (zeroed again when the tags wrap)
     uint64_t* stamps = nullptr;  // wq_debug_set_timeline
     // the pipelined heavy tick (wq_route.hip, short ticks): count chunks on `side` while the launch
     // stream scans and emits the previous chunk; {P, F} carried across the chunks' scans
@@ -207,7 +208,7 @@ struct wq_router {
     // the one-pass slot grouping (wq_shard.hip slot_group_kernel): tagged look-back granules per
     // (owner, block), zeroed once per allocation (tag 0 never matches), and the launches so far
     wq::DevBuf shard_look;
-    uint64_t shard_look_zeroed = 0, shard_look_calls = 0;
+    uint64_t shard_look_zeroed = 0, shard_look_calls = 0, shard_look_epoch = 0;
     int route_cfg = 0;  // route kernel shapes (wq_route.hip kCfgs)
     uint32_t route_chunks = 0;  // wq_debug_set_route_chunks: chunks of the pipelined heavy tick (0 = default)
     bool heavy_fanout = false;  // wq_set_fanout_hint: default shape -> kCfgHeavy

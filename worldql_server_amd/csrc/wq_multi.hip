@@ -247,10 +247,10 @@ int tick_into(wq_router* h, uint32_t g, const SliceIn& x, bool msgs, bool view) 
         WQ_HIP(s, hipMemcpyAsync(&c, s->rws.last, sizeof(c), hipMemcpyDeviceToHost, s->stream));
         WQ_HIP(s, hipStreamSynchronize(s->stream));
         if (x.M == 0) c.n_pairs = 0;
+        Pr = c.n_pairs;  // also of a tick past the limit: multi_route_tick reports the sum
         if (c.error & 4u) return set_error(s, WQ_E_TIMEOUT, "route look-back spin gave up");
         if (c.error & 8u) return set_error(s, WQ_E_INVALID, "a replica's table still misses a device batch");
         if (c.error) return set_error(s, WQ_E_CAPACITY, "more than 2^32-1 pairs in one tick");
-        Pr = c.n_pairs;
         // the next tick's shape from this one's fan-out, as the host-array tick does (a replica's
         // device ticks are read back here anyway)
         if (s->fanout_auto && x.M >= 256) s->heavy_fanout = (double)c.n_pairs >= WQ_HEAVY_FANOUT * (double)x.M;
@@ -503,9 +503,14 @@ int multi_route_tick(wq_router* h, const double* pos, const int64_t* keys, const
                   reinterpret_cast<const uint8_t*>(din + o_r), Mg};
         return tick_into(h, g, x, msgs != nullptr, false);
     });
-    if (rc) return rc;
     std::vector<uint64_t> base(G + 1, 0);
     for (uint32_t g = 0; g < G; ++g) base[g + 1] = base[g] + m.P[g];
+    if (rc == WQ_E_CAPACITY) {
+        // a sub-handle's own tick was past the u32 offsets' limit (a short staging is grown inside
+        // tick_into, never reported): so is the whole tick's P, the sum where every sub-handle reported
+        *n_pairs = std::max<uint64_t>(base[G], 1ull << 32);
+    }
+    if (rc) return rc;
     const uint64_t P = base[G];
     *n_pairs = P;
     if (P > 0xFFFFFFFFull) return set_error(h, WQ_E_CAPACITY, "more than 2^32-1 pairs in one tick");

@@ -176,9 +176,15 @@ int launch_route(wq_router* h, const double* d_pos, const int64_t* d_keys, const
     if (cfg.tick && !radius) {  // single launch: one block per 256 messages, decoupled look-back
         const uint64_t nb = (M + kBlock - 1) / kBlock;
         WQ_ALLOC(h, rw.agg, 2 * nb * 8);
-        if (rw.agg_zeroed < 2 * nb) {  // fresh granules: tag 0 never matches a call's tag
+        // fresh granules (tag 0 never matches a call's tag), and all of them again each time the
+        // tags wrap: between two calls that share a tag lies exactly one multiple of the period, so
+        // a granule left by a longer tick one period back can never pass for this call's (a tick of
+        // many blocks, a period of shorter ticks, a tick of many blocks again)
+        const uint64_t epoch = rw.calls / kTickTagPeriod;
+        if (rw.agg_zeroed < 2 * nb || epoch != rw.agg_epoch) {
             WQ_HIP(h, hipMemsetAsync(rw.agg.p, 0, rw.agg.bytes, s));
             rw.agg_zeroed = rw.agg.bytes / 8;
+            rw.agg_epoch = epoch;
         }
         TickParams tp;
         tp.in = in;
@@ -187,7 +193,7 @@ int launch_route(wq_router* h, const double* d_pos, const int64_t* d_keys, const
         tp.out = EmitOut{d_sender, capacity ? d_peers : nullptr, d_msgs, capacity, d_pos, d_repl};
         tp.look = rw.agg.as<uint64_t>();
         tp.fgran = tp.look + nb;
-        tp.tag = (uint32_t)(rw.calls % ((1ull << 30) - 1)) + 1u;
+        tp.tag = (uint32_t)(rw.calls % kTickTagPeriod) + 1u;
         tp.cnt = cur;
         tp.cnt_next = nxt;
         tp.health = route_health(h);

@@ -395,6 +395,28 @@ int wq_debug_set_route_chunks(wq_router* h, int chunks) {
     return WQ_OK;
 }
 
+int wq_debug_set_route_calls(wq_router* h, uint64_t calls) {
+    if (!h || h->multi) return WQ_E_INVALID;
+    WQ_HIP(h, hipSetDevice(h->device));
+    RouteWs& rw = h->rws;
+    // the counter ring is indexed by the call counter's parity and each call zeroes the next call's
+    // slot: after a jump both slots start from zero, as after an empty tick (route_counters)
+    if (!rw.buf.p) {
+        WQ_ALLOC(h, rw.buf, 128);
+        WQ_HIP(h, hipMemsetAsync(rw.buf.p, 0, 128, h->stream));
+    } else {
+        WQ_HIP(h, hipMemsetAsync(rw.buf.as<char>() + 64, 0, 2 * sizeof(wq_route_counters), h->stream));
+    }
+    rw.calls = calls;
+    return WQ_OK;
+}
+
+int wq_debug_route_calls(wq_router* h, uint64_t* calls) {
+    if (!h || !calls || h->multi) return WQ_E_INVALID;
+    *calls = h->rws.calls;
+    return WQ_OK;
+}
+
 int wq_debug_update_counts(wq_router* h, uint64_t* incremental, uint64_t* rebuild_fallbacks,
                            uint64_t* wave_batches) {
     if (!h || !incremental || !rebuild_fallbacks || !wave_batches) return WQ_E_INVALID;
@@ -487,12 +509,15 @@ int wq_route_tick_device(wq_router* h, const double* d_pos, const int64_t* d_key
         size_t P = 0;
         const int rc = multi_route_tick(h, d_pos, d_keys, d_world, d_sender, d_repl, n_msgs, d_offsets, d_peers, d_msgs,
                                         capacity, &P, true);
+        const bool past_limit = P > 0xFFFFFFFFull;  // more pairs than u32 offsets hold: error bit 2
         if ((rc == WQ_OK || rc == WQ_E_CAPACITY) && d_counters) {  // P (F reported as P), overflow
-            wq_route_counters c{P, P, P > capacity ? 1u : 0u, 0u};
+            wq_route_counters c{P, P, P > capacity ? 1u : 0u, past_limit ? 2u : 0u};
             WQ_HIP(h, hipMemcpyAsync(d_counters, &c, sizeof(c), hipMemcpyHostToDevice, h->stream));
             WQ_HIP(h, hipStreamSynchronize(h->stream));
         }
-        return rc == WQ_E_CAPACITY ? WQ_OK : rc;  // as the single-GPU form: the counters report overflow
+        // a short capacity as the single-GPU form reports it: WQ_OK, the counters carry the overflow.
+        // A tick past the limit is WQ_E_CAPACITY here: this form is synchronous, and its offsets are void
+        return rc == WQ_E_CAPACITY && !past_limit ? WQ_OK : rc;
     }
     // the three-launch shape's scan writes d_counters itself once they are final (no copy launch)
     h->rws.out = d_counters;

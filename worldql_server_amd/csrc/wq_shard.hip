@@ -613,7 +613,7 @@ constexpr int kGroupTiles = 2;
 
 struct GroupArgs {
     uint64_t* look;  // [G * nblk] granules
-    uint32_t tag;    // this launch's tag, 1 .. 2^30 - 1
+    uint32_t tag;    // this launch's tag, 1 .. 2^22 - 1
     uint32_t* a;     // the A vector: {count, status} per owner
     // the owner form's in-place self segment: its {count, status} straight into the received A
     // vector as well (the exchange then skips the self copy), nullable
@@ -661,10 +661,10 @@ __global__ void __launch_bounds__(kBlock)
             const int64_t idx = hi - (int64_t)k;
             uint64_t v = 0;
             if (!done && idx >= 0) v = poll_granule(g.look + (uint64_t)d * NB + idx, g.tag, &gave_up);
-            const bool isP = !done && idx >= 0 && ((uint32_t)(v >> 32) & 3u) == kFlagP;
+            const bool isP = !done && idx >= 0 && granule_flag(v) == kFlagP;
             const uint64_t pm = __ballot(isP) & gmask;
             const uint32_t first = pm ? (uint32_t)__builtin_ctzll(pm) - d * W : W;  // nearest inclusive prefix
-            uint64_t x = (!done && idx >= 0 && k <= first) ? (uint32_t)v : 0u;
+            uint64_t x = (!done && idx >= 0 && k <= first) ? granule_value(v) : 0ull;
             for (uint32_t o = W >> 1; o >= 1; o >>= 1) x += __shfl_xor(x, (int)o, 64);  // the group's sum
             if (!done) acc += x;
             // the group is done at an inclusive prefix or past block 0
@@ -898,11 +898,15 @@ int launch_budget_slots(wq_router* h, const double* d_pos, const int64_t* d_keys
         in.nblk = (uint32_t)((M + kGroupTiles * kShardTile - 1) / (kGroupTiles * kShardTile));
         const uint64_t ng = (uint64_t)G * in.nblk;
         WQ_ALLOC(h, h->shard_look, ng * 8);
-        if (h->shard_look_zeroed < ng) {  // fresh granules: tag 0 never matches a launch's tag
+        // fresh granules (tag 0 never matches a launch's tag), and all of them again each time the tags
+        // wrap (route_tick.hpp kTickTagPeriod), so a granule left one period back cannot pass for this launch's
+        const uint64_t epoch = h->shard_look_calls / kTickTagPeriod;
+        if (h->shard_look_zeroed < ng || epoch != h->shard_look_epoch) {
             WQ_HIP(h, hipMemsetAsync(h->shard_look.p, 0, h->shard_look.bytes, s));
             h->shard_look_zeroed = h->shard_look.bytes / 8;
+            h->shard_look_epoch = epoch;
         }
-        GroupArgs ga{h->shard_look.as<uint64_t>(), (uint32_t)(h->shard_look_calls++ % ((1ull << 30) - 1)) + 1u, d_a,
+        GroupArgs ga{h->shard_look.as<uint64_t>(), (uint32_t)(h->shard_look_calls++ % kTickTagPeriod) + 1u, d_a,
                      a_self, me};
         if (d_keys)
             hipLaunchKernelGGL((slot_group_kernel<true>), dim3(in.nblk), dim3(kBlock), 0, s, in, L, d_slots, d_perm, ga);

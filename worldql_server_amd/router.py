@@ -111,6 +111,8 @@ def load_library(build_if_missing: bool = True):
         "wq_debug_set_route_config": ([vp, i32], i32),
         "wq_debug_set_route_chunks": ([vp, i32], i32),
         "wq_debug_route_config_count": ([], i32),
+        "wq_debug_set_route_calls": ([vp, ctypes.c_uint64], i32),
+        "wq_debug_route_calls": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
         "wq_debug_set_timeline": ([vp, vp], i32),
         "wq_debug_update_counts": ([vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3, i32),
         "wq_set_peer_positions": ([vp, vp, sz], i32),
@@ -322,7 +324,8 @@ class Router:
             n = ctypes.c_size_t()
             rc = self.lib.wq_route_tick(self.h, _p(pos_a), _p(keys_a), _p(world), _p(sender), _p(repl), M,
                                         _p(offsets), _p(peers), _p(msgs), cap, ctypes.byref(n))
-            if rc == abi.WQ_E_CAPACITY and n.value > cap and capacity is None:
+            # (more pairs than the u32 offsets hold is WQ_E_CAPACITY too: no buffer cures it, raised below)
+            if rc == abi.WQ_E_CAPACITY and cap < n.value <= abi.MAX_PAIRS and capacity is None:
                 cap = n.value
                 continue
             self._check(rc)
@@ -352,7 +355,8 @@ class Router:
             n = ctypes.c_size_t()
             rc = self.lib.wq_route_global(self.h, _p(world), _p(sender), _p(repl), M, _p(offsets), _p(peers),
                                           _p(msgs), cap, ctypes.byref(n))
-            if rc == abi.WQ_E_CAPACITY and n.value > cap and capacity is None:
+            # (more pairs than the u32 offsets hold is WQ_E_CAPACITY too: no buffer cures it, raised below)
+            if rc == abi.WQ_E_CAPACITY and cap < n.value <= abi.MAX_PAIRS and capacity is None:
                 cap = n.value
                 continue
             self._check(rc)
@@ -747,6 +751,17 @@ class Router:
     def set_route_chunks(self, chunks: int) -> None:
         """Chunks of the pipelined heavy tick (wq_debug_set_route_chunks; 0 = default)."""
         self._check(self.lib.wq_debug_set_route_chunks(self.h, chunks))
+
+    def route_calls(self) -> int:
+        """The handle's route-call counter (wq_debug_route_calls): the single-launch tick's granule tag
+        is this counter modulo abi.TICK_TAG_PERIOD, plus one."""
+        n = ctypes.c_uint64()
+        self._check(self.lib.wq_debug_route_calls(self.h, ctypes.byref(n)))
+        return n.value
+
+    def set_route_calls(self, calls: int) -> None:
+        """wq_debug_set_route_calls: a test hook that moves the route-call counter."""
+        self._check(self.lib.wq_debug_set_route_calls(self.h, calls))
 
     # ---- instrumentation ----
     def profile_enable(self, on: bool = True) -> None:
