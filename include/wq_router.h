@@ -579,7 +579,32 @@ int wq_sharded_route_owner_slots_async(wq_router* h, const double* d_pos, const 
  * peer p < n_peers whose bit is set in d_connected (bit p % 32 of word p / 32; NULL = every peer
  * connected) the messages it must receive, ascending — the reference's "recipients intersected
  * with the connected peers". d_peer_offsets[n_peers + 1]; d_msgs_out[n_pairs] (the kept ones
- * first: d_peer_offsets[n_peers] of them). n_pairs = d_offsets[n_msgs]. Asynchronous. */
+ * first: d_peer_offsets[n_peers] of them). Asynchronous: nothing is read back, so the call can
+ * follow wq_route_tick_device on the same stream without the host knowing the tick's pair count.
+ *
+ * Inputs
+ *   - n_pairs is the element count of d_peers and d_msgs_out, i.e. the `capacity` the tick was
+ *     given. It need not equal d_offsets[n_msgs]: a cut tick's offsets reach past it, a buffer
+ *     larger than the tick's pairs ends behind them.
+ *   - Row m is the part of [offsets[m], offsets[m + 1]) inside [0, n_pairs). It is empty when
+ *     offsets[m + 1] < offsets[m]. Elements of [0, n_pairs) that no row covers belong to nobody
+ *     and are dropped, whatever they hold.
+ *   - No input is dereferenced outside [0, n_pairs), [0, n_msgs] or the ceil(n_peers / 32) bitmap
+ *     words, whatever the arrays hold. d_offsets is not read at all with n_msgs == 0.
+ * Outputs
+ *   - Nothing is written outside d_peer_offsets[0 .. n_peers] and d_msgs_out[0 .. n_pairs).
+ *   - For ascending offsets the result is exactly the transpose of the clamped rows: a peer's
+ *     messages ascend, and a peer repeated within a row keeps its repeats. A tick always writes
+ *     ascending offsets, cut or not, below the 2^32-pair limit.
+ *   - For other offsets (wrapped, descending, junk) the result is unspecified but well formed:
+ *     d_peer_offsets ascends from 0, d_peer_offsets[n_peers] <= n_pairs, every written message
+ *     index is < n_msgs, and two calls on the same input give the same bytes.
+ *   - d_msgs_out[d_peer_offsets[n_peers] .. n_pairs) is scratch: it holds the rows of the dropped
+ *     elements, 0 for an element no row covers.
+ *   - d_peer_offsets is always written in full, including n_msgs == 0, n_pairs == 0 and
+ *     n_peers == 0.
+ * Scratch lives in the handle, grow-only (12 n_pairs bytes and the sort's): a steady-state call
+ * does no hipMalloc. */
 int wq_peer_major_device(wq_router* h, const uint32_t* d_offsets, const uint32_t* d_peers, size_t n_msgs,
                          size_t n_pairs, const uint32_t* d_connected, uint32_t n_peers,
                          uint32_t* d_peer_offsets, uint32_t* d_msgs_out);

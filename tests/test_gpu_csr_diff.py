@@ -193,6 +193,15 @@ def _check_tick(prev, cur, out, n_peers, tracker):
     po, rows = tracker.peer_major("entered", None, n_peers)
     w_po, w_rows = interest.peer_major_np(want[0], want[1], n_peers)
     _bytes_equal((_host(po), _host(rows)), (w_po, w_rows))
+    # the same with a connected bitmap: about a third of the observers are dropped
+    n_seen = n_peers - 3
+    conn = np.packbits(np.random.default_rng(ne).random(((n_seen + 31) // 32) * 32) < 0.66,
+                       bitorder="little").view(np.uint32)
+    d_conn = _dev(conn)
+    po, rows = tracker.peer_major("entered", d_conn.data_ptr(), n_seen)
+    w_po, w_rows = interest.peer_major_np(want[0], want[1], n_seen, conn)
+    assert ne == 0 or 0 < len(w_rows) < ne
+    _bytes_equal((_host(po), _host(rows)), (w_po, w_rows))
     return ne, nl
 
 

@@ -81,17 +81,45 @@ def clamp_csr_np(offsets, peers, capacity: int | None = None):
     return pre.astype(np.uint32), np.ascontiguousarray(peers[idx], dtype=np.uint32), cut
 
 
-def peer_major_np(offsets, peers, n_peers: int):
+def peer_major_np(offsets, peers, n_peers: int, connected=None, capacity: int | None = None):
     """The transpose of a CSR: (peer_offsets[n_peers + 1], rows) — per peer the rows that hold it,
-    ascending (what wq_peer_major_device writes with every peer connected)."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-    peers = np.ascontiguousarray(peers, dtype=np.uint32)[: int(offsets[-1])]
-    rows = np.repeat(np.arange(len(offsets) - 1, dtype=np.uint32), np.diff(offsets.astype(np.int64)))
-    keep = peers < n_peers
-    order = np.argsort(peers[keep], kind="stable")
+    ascending; the definition of what wq_peer_major_device writes for ascending offsets.
+
+    Row m is the part of [offsets[m], offsets[m + 1]) inside [0, capacity) (capacity: the element
+    count of `peers`, the default — a cut tick's offsets reach past it, a padded buffer's end before
+    it; elements no row covers belong to nobody). A pair is kept when its peer is below n_peers and,
+    with `connected` (u32 words, bit p % 32 of word p // 32), its bit is set. The kept pairs are
+    sorted stably by peer: a peer's rows ascend, and a peer repeated within a row keeps its repeats.
+    `offsets` of length 0 or 1 is a CSR without rows."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).astype(np.int64)
+    peers = np.ascontiguousarray(peers, dtype=np.uint32)
+    cap = len(peers) if capacity is None else int(capacity)
+    if cap > len(peers):
+        raise ValueError("capacity is the element count of peers: it cannot exceed len(peers)")
+    n_peers = int(n_peers)
+    M = max(len(off) - 1, 0)
+    if M and (np.diff(off) < 0).any():
+        raise ValueError("offsets must ascend (for others the kernel's result is unspecified)")
+    a = np.minimum(off[:M], cap)
+    b = np.minimum(off[1:M + 1], cap)
+    n = b - a
+    total = int(n.sum())
+    rows = np.repeat(np.arange(M, dtype=np.uint32), n)
+    idx = np.repeat(a - (np.cumsum(n) - n), n) + np.arange(total, dtype=np.int64)
+    p = peers[idx]
+    keep = p < n_peers
+    if connected is not None:
+        words = np.ascontiguousarray(connected, dtype=np.uint32)
+        q = np.where(keep, p, 0).astype(np.int64)
+        if keep.any() and int(q.max()) >> 5 >= len(words):
+            raise ValueError("connected needs ceil(n_peers / 32) words")
+        bit = (words[q >> 5] >> (q & 31).astype(np.uint32)) & np.uint32(1) if len(words) else np.zeros(total, np.uint32)
+        keep &= bit == 1
+    p, rows = p[keep], rows[keep]
+    order = np.argsort(p, kind="stable")
     po = np.zeros(n_peers + 1, dtype=np.uint32)
-    np.cumsum(np.bincount(peers[keep].astype(np.int64), minlength=n_peers)[:n_peers], out=po[1:])
-    return po, rows[keep][order]
+    np.cumsum(np.bincount(p.astype(np.int64), minlength=n_peers)[:n_peers], out=po[1:])
+    return po, np.ascontiguousarray(rows[order], dtype=np.uint32)
 
 
 class InterestTracker:
