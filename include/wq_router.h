@@ -676,6 +676,73 @@ int wq_csr_diff(wq_router* h, size_t n_rows,
                 uint32_t* left_offsets, uint32_t* left_peers, size_t left_capacity,
                 size_t* n_entered, size_t* n_left);
 
+/* ---- send budgets: of every peer's send list the B nearest messages ----
+ * wq_peer_major_device gives every observer all it could be told this tick; a connection has a
+ * budget. This call keeps, per peer, the min(B, len) messages nearest to the peer and leaves the
+ * rest for a later tick. An extension like the radius filter, follow and the interest diff: the
+ * reference routes and forgets (local_message.rs:52-86, peer_map.rs:151-163) and has no budget.
+ *
+ * Input rows
+ *   - d_peer_offsets[n_peers + 1] and d_msgs[n_in] are a peer-major CSR, what wq_peer_major_device
+ *     writes. n_in is the element count of d_msgs and of d_out_msgs.
+ *   - Row p is the part of [d_peer_offsets[p], d_peer_offsets[p + 1]) inside [0, n_in), empty when
+ *     the offsets descend.
+ *   - d_msg_pos[3 n_msgs] are the tick's message positions. d_peer_pos[3 n_peer_pos] are the peers'
+ *     positions; NULL (with n_peer_pos 0): the handle's wq_set_peer_positions[_device]. A non-NULL
+ *     d_peer_pos with n_peer_pos 0 is an explicit "no peer has a position" and is not read.
+ *   - No input is dereferenced outside [0, n_in), [0, n_peers], [0, 3 n_msgs), [0, 3 n_peer_pos) or
+ *     d_budget[0 .. n_peers), whatever the arrays hold.
+ *   - Offsets that descend can make the clamped rows overlap. The rows are walked up to n_in
+ *     elements in total: the row that passes it is cut there and the rows behind it are empty.
+ *     Ascending offsets never reach that. `error` bit 0 is set, and the result is the contract
+ *     below applied to those rows.
+ * Key of element j of row p, with message index m = d_msgs[j]
+ *   - dx = mx - px; dy = my - py; dz = mz - pz; d2 = (dx*dx + dy*dy) + dz*dz, in f64, left to right,
+ *     no FMA contraction: the radius filter's expression ("C5: exact radius filter" above).
+ *   - d2 counts as +infinity when it is NaN, when m >= n_msgs (this also sets `error` bit 1) or when
+ *     p >= n_peer_pos; such an element never reads a position it does not have.
+ *   - Elements order by (d2, position in the input row): a total order. Co-located entities have
+ *     equal d2, and a row may hold a message twice.
+ * Output
+ *   - Row p of the output holds the min(B_p, len_p) smallest elements of row p, B_p = d_budget[p],
+ *     or k when d_budget is NULL, in input order (a stable compaction: ascending messages stay
+ *     ascending). B_p == 0 empties the row; B_p >= len_p copies it.
+ *   - d_out_offsets[0 .. n_peers] is always written in full, from 0, including n_in == 0 and
+ *     n_peers == 0.
+ *   - Nothing is written outside d_out_offsets[0 .. n_peers] and d_out_msgs[0 .. n_kept); n_kept <=
+ *     n_in, so the output never overflows. The output must not alias the input.
+ *   - d_counters is nullable.
+ *   - Output is deterministic, byte for byte: placement comes from counts and prefix sums, never
+ *     from atomic arrival order (the atomics are integer adds into histograms).
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. The grids are sized from n_in and
+ *     n_peers. No lane, wave or block walks a row: a row longer than 256 elements is selected by a
+ *     radix select whose histograms all its elements build, a shorter one is ranked by counting.
+ *   - Scratch lives in the handle, grow-only: at most 18 n_in + 12 (n_peers + 1) bytes plus the
+ *     scans' (each buffer is allocated a quarter above its need). A steady-state call does no
+ *     hipMalloc.
+ * Limits and handle kinds
+ *   - n_in <= 2^32 - 1 and n_peers < 2^32 - 1; n_msgs and n_peer_pos above 2^32 - 1 count as that.
+ *   - WQ_E_INVALID for a null handle, a null required array with a non-zero size (d_out_offsets is
+ *     always required), d_peer_pos == NULL when the handle has no positions, and d_peer_pos == NULL
+ *     on a multi-GPU handle, whose positions live in its sub-handles. Nothing is launched then.
+ *   - With explicit positions a multi-GPU handle runs the call on its own stream with the arrays on
+ *     devices[0], as wq_peer_major_device does. */
+typedef struct wq_budget_counters {
+    uint64_t n_in;       /* elements inside the clamped input rows */
+    uint64_t n_kept;     /* elements written = out_offsets[n_peers] */
+    uint32_t rows_cut;   /* rows longer than their budget */
+    uint32_t error;      /* bit 0: an input row had off[p+1] < off[p] or reached past n_in;
+                            bit 1: some element's message index was >= n_msgs */
+} wq_budget_counters;
+int wq_peer_budget_device(wq_router* h,
+        const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
+        const double* d_msg_pos, size_t n_msgs,
+        const double* d_peer_pos, size_t n_peer_pos,
+        uint32_t k, const uint32_t* d_budget,
+        uint32_t* d_out_offsets, uint32_t* d_out_msgs,
+        wq_budget_counters* d_counters);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

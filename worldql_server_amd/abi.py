@@ -50,6 +50,12 @@ DIFF_OVERFLOW_ENTERED = 1  # wq_diff_counters.overflow bits
 DIFF_OVERFLOW_LEFT = 2
 DIFF_ERROR_ROWS = 1        # wq_diff_counters.error bit 0: a row was cut to the part inside bounds
 
+# struct wq_budget_counters: 24 bytes (wq_peer_budget_device)
+BUDGET_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_kept", np.uint64),
+                                  ("rows_cut", np.uint32), ("error", np.uint32)])
+BUDGET_ERROR_ROWS = 1      # wq_budget_counters.error bit 0: a row descended or reached past n_in
+BUDGET_ERROR_MSG = 2       # bit 1: a message index was >= n_msgs
+
 
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]

@@ -244,6 +244,13 @@ struct wq_router {
     // call zeroes the next call's) followed by the host form's counters
     wq::DevBuf diff_len, diff_pre, diff_cnt, diff_base, diff_flags, diff_err;
     uint64_t diff_calls = 0;
+    // send budgets (wq_budget.hip): per peer the clamped lengths / kept counts, their saturating prefix
+    // and the ordinal space; per ordinal the key, row and class; per slot of kBudShort ordinals the
+    // select's state and histogram; per granule of 64 the tie and keep flag words, counts and prefixes;
+    // {rows_cut, error}
+    wq::DevBuf bud_len, bud_sum, bud_pre, bud_key, bud_row, bud_cls, bud_sel, bud_hist, bud_words, bud_cnt, bud_base,
+        bud_ctrl;
+    size_t bud_hist_clean = 0;  // bytes of bud_hist known to be zero (0: clear before the next select)
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -341,6 +348,13 @@ int launch_csr_diff(wq_router* h, size_t n_rows, const uint32_t* d_old_offsets, 
                     uint32_t* d_left_offsets, uint32_t* d_left_peers, size_t left_capacity,
                     wq_diff_counters* d_counters, bool own);
 void csr_diff_release(wq_router* h);
+// wq_budget.hip: the send budgets on device arrays (asynchronous; the positions already resolved),
+// and its scratch's release.
+int launch_peer_budget(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
+                       size_t n_in, const double* d_msg_pos, size_t n_msgs, const double* d_peer_pos,
+                       size_t n_peer_pos, uint32_t k, const uint32_t* d_budget, uint32_t* d_out_offsets,
+                       uint32_t* d_out_msgs, wq_budget_counters* d_counters);
+void budget_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
 // wq_table_export.hip: frees the export's scratch.

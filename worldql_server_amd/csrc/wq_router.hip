@@ -125,6 +125,7 @@ int wq_router_destroy(wq_router* h) {
     shard_release(h);
     follow_release(h);
     csr_diff_release(h);
+    budget_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -676,6 +677,28 @@ int wq_peer_major_device(wq_router* h, const uint32_t* d_offsets, const uint32_t
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_peer_major(h, d_offsets, d_peers, n_msgs, n_pairs, d_connected, n_peers, d_peer_offsets,
                              d_msgs_out);
+}
+
+int wq_peer_budget_device(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
+                          size_t n_in, const double* d_msg_pos, size_t n_msgs, const double* d_peer_pos,
+                          size_t n_peer_pos, uint32_t k, const uint32_t* d_budget, uint32_t* d_out_offsets,
+                          uint32_t* d_out_msgs, wq_budget_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!d_out_offsets || (n_peers && !d_peer_offsets) || (n_in && (!d_msgs || !d_out_msgs)) ||
+        (n_msgs && !d_msg_pos) || (!d_peer_pos && n_peer_pos))
+        return set_error(h, WQ_E_INVALID, "peer_budget: a null array with a non-zero size");
+    if (n_in > 0xFFFFFFFFull || n_peers == 0xFFFFFFFFu)
+        return set_error(h, WQ_E_INVALID, "peer_budget: n_in must be <= 2^32 - 1 and n_peers < 2^32 - 1");
+    if (!d_peer_pos) {
+        if (h->multi)
+            return set_error(h, WQ_E_INVALID, "peer_budget: a multi-GPU handle needs explicit peer positions");
+        if (!h->n_ppos) return set_error(h, WQ_E_INVALID, "peer_budget: no peer positions (wq_set_peer_positions)");
+        d_peer_pos = h->ppos.as<double>();
+        n_peer_pos = h->n_ppos;
+    }
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_peer_budget(h, d_peer_offsets, d_msgs, n_peers, n_in, d_msg_pos, n_msgs, d_peer_pos, n_peer_pos, k,
+                              d_budget, d_out_offsets, d_out_msgs, d_counters);
 }
 
 // The argument rules both forms of wq_csr_diff share (capacities already clamped to 2^32 - 1).

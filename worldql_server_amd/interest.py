@@ -5,6 +5,10 @@ wq_csr_diff*; kernels: csrc/wq_csr_diff.hip).
 `clamp_csr_np` is the definition of how the kernels read offsets that do not describe a CSR;
 `InterestTracker` is the convenience a server that replicates entities uses: route a tick, get the
 observers that entered and left every entity's interest set since the previous tick.
+
+`peer_major_np` is the definition of the per-peer send lists (wq_peer_major_device) and
+`peer_budget_np` the definition of the send budgets that follow them (wq_peer_budget_device,
+csrc/wq_budget.hip): of every peer's list the min(budget, len) messages nearest to the peer.
 """
 from __future__ import annotations
 
@@ -122,6 +126,66 @@ def peer_major_np(offsets, peers, n_peers: int, connected=None, capacity: int | 
     return po, np.ascontiguousarray(rows[order], dtype=np.uint32)
 
 
+def budget_keys_np(msgs, msg_pos, peer_pos, p: int):
+    """The keys of row p's elements `msgs` (message indices): the radius filter's f64 squared distance
+    (dx*dx + dy*dy) + dz*dz, left to right; +inf for NaN, for a message index >= len(msg_pos) and for a
+    peer without a position."""
+    msgs = np.asarray(msgs, dtype=np.int64)
+    d2 = np.full(len(msgs), np.inf, dtype=np.float64)
+    if p >= len(peer_pos) or not len(msgs):
+        return d2
+    ok = msgs < len(msg_pos)
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = msg_pos[msgs[ok]] - peer_pos[p][None, :]
+        v = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    d2[ok] = np.where(np.isnan(v), np.inf, v)
+    return d2
+
+
+def peer_budget_np(peer_offsets, msgs, msg_pos, peer_pos, k=None, budget=None):
+    """Send budgets, the definition of what wq_peer_budget_device writes: of every row of the
+    peer-major CSR (peer_offsets[n_peers + 1], msgs[n_in]) the min(B_p, len_p) elements nearest to
+    the peer, in input order. Returns (out_offsets[n_peers + 1], out_msgs[n_kept], counters) with
+    counters a dict of n_in, n_kept, rows_cut, error.
+
+    Row p is the part of [peer_offsets[p], peer_offsets[p + 1]) inside [0, n_in), empty when the
+    offsets descend; the rows are walked up to n_in elements in total (only offsets that descend get
+    there: the row that passes n_in is cut, the ones behind it are empty; error bit 0). B_p is
+    budget[p], or k for everyone. Elements order by (d2, position in the row), d2 from
+    budget_keys_np. error bit 1: a message index >= len(msg_pos). Row by row, for clarity."""
+    off = np.ascontiguousarray(peer_offsets, dtype=np.uint32).astype(np.int64)
+    msgs = np.ascontiguousarray(msgs, dtype=np.uint32)
+    msg_pos = np.ascontiguousarray(msg_pos, dtype=np.float64).reshape(-1, 3)
+    peer_pos = np.ascontiguousarray(peer_pos, dtype=np.float64).reshape(-1, 3)
+    n_in, n_peers = len(msgs), max(len(off) - 1, 0)
+    if budget is None and k is None:
+        raise ValueError("give k or a per-peer budget")
+    out_off = np.zeros(n_peers + 1, dtype=np.uint32)
+    out, walked, rows_cut, error = [], 0, 0, 0
+    for p in range(n_peers):
+        a, b = min(off[p], n_in), min(off[p + 1], n_in)
+        b = max(a, b)
+        if off[p] > off[p + 1] or off[p + 1] > n_in:
+            error |= 1
+        n = min(b - a, n_in - walked)
+        if n != b - a:
+            error |= 1
+        walked += n
+        row = msgs[a:a + n]
+        B = int(budget[p]) if budget is not None else int(k)
+        if (row.astype(np.int64) >= len(msg_pos)).any():
+            error |= 2
+        if n > B:
+            rows_cut += 1
+            d2 = budget_keys_np(row, msg_pos, peer_pos, p)
+            order = np.lexsort((np.arange(n), d2))      # by d2, then position
+            row = row[np.sort(order[:B])]               # the B nearest, back in input order
+        out.append(row)
+        out_off[p + 1] = out_off[p] + len(row)
+    out_msgs = np.concatenate(out).astype(np.uint32) if out else np.zeros(0, np.uint32)
+    return out_off, out_msgs, dict(n_in=walked, n_kept=int(out_off[-1]), rows_cut=rows_cut, error=error)
+
+
 class InterestTracker:
     """Routes ticks of `n_rows` entities (row m of every tick = entity m) and keeps the previous
     tick's CSR on the device, so every `route` also returns who entered and who left each row.
@@ -220,3 +284,25 @@ class InterestTracker:
         torch.cuda.synchronize(self.dev)
         kept = int(po[n_peers].item()) & 0xFFFFFFFF
         return po, rows[:kept]
+
+    def peer_budget(self, peer_offsets, rows, msg_pos_ptr: int, k: int | None = None, budget_ptr: int | None = None,
+                    peer_pos_ptr: int | None = None, n_peer_pos: int = 0):
+        """Chains after peer_major: of every observer's list (peer_offsets, rows — the tensors peer_major
+        returned) the min(budget, len) entities nearest to it, in input order, through
+        wq_peer_budget_device: (out_offsets[n_peers + 1], out_rows[kept]). msg_pos_ptr: the tick's
+        n_rows x 3 f64 positions on the device; the observers' positions are the router's
+        set_peer_positions unless peer_pos_ptr / n_peer_pos give others; budget_ptr: u32 per observer,
+        else k for everyone."""
+        torch = self.torch
+        if k is None and budget_ptr is None:
+            raise ValueError("give k or budget_ptr")
+        n_peers, n_in = peer_offsets.numel() - 1, rows.numel()
+        oo = torch.empty(n_peers + 1, dtype=torch.int32, device=self.dev)
+        om = torch.empty(max(n_in, 1), dtype=torch.int32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self.router.peer_budget_device(peer_offsets.data_ptr(), rows.data_ptr() if n_in else None, n_peers, n_in,
+                                       msg_pos_ptr, self.n_rows, peer_pos_ptr, n_peer_pos, k or 0, budget_ptr,
+                                       oo.data_ptr(), om.data_ptr() if n_in else None, None)
+        torch.cuda.synchronize(self.dev)
+        kept = int(oo[n_peers].item()) & 0xFFFFFFFF
+        return oo, om[:kept]

@@ -77,6 +77,7 @@ def load_library(build_if_missing: bool = True):
         "wq_route_global": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_route_global_device": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, vp], i32),
         "wq_peer_major_device": ([vp, vp, vp, sz, sz, vp, u32, vp, vp], i32),
+        "wq_peer_budget_device": ([vp, vp, vp, u32, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -376,6 +377,19 @@ class Router:
         self._check(self.lib.wq_peer_major_device(self.h, offsets_ptr or None, peers_ptr or None, n_msgs, n_pairs,
                                                   connected_ptr or None, n_peers, peer_offsets_ptr,
                                                   msgs_out_ptr or None))
+
+    def peer_budget_device(self, peer_offsets_ptr: int | None, msgs_ptr: int | None, n_peers: int, n_in: int,
+                           msg_pos_ptr: int | None, n_msgs: int, peer_pos_ptr: int | None, n_peer_pos: int, k: int,
+                           budget_ptr: int | None, out_offsets_ptr: int | None, out_msgs_ptr: int | None,
+                           counters_ptr: int | None = None) -> None:
+        """wq_peer_budget_device: of every row of a peer-major CSR the min(budget, len) messages nearest to
+        the peer, in input order; asynchronous on the handle's stream. peer_pos_ptr None: the handle's
+        set_peer_positions. The counters (abi.BUDGET_COUNTERS_DTYPE) stay where counters_ptr points.
+        Host definition: interest.peer_budget_np."""
+        self._check(self.lib.wq_peer_budget_device(self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in,
+                                                   msg_pos_ptr or None, n_msgs, peer_pos_ptr or None, n_peer_pos, k,
+                                                   budget_ptr or None, out_offsets_ptr or None, out_msgs_ptr or None,
+                                                   counters_ptr or None))
 
     # ---- interest changes between two ticks (include/wq_router.h; host reference: interest.py) ----
     def csr_diff(self, old_offsets, old_peers, new_offsets, new_peers, with_left: bool = True,
