@@ -743,6 +743,73 @@ int wq_peer_budget_device(wq_router* h,
         uint32_t* d_out_offsets, uint32_t* d_out_msgs,
         wq_budget_counters* d_counters);
 
+/* ---- byte budgets: of every peer's send list the nearest messages that fit in W bytes ----
+ * A connection's budget is bytes per tick, and frames differ in size by orders of magnitude
+ * (wq_serialize_messages returns every frame's size as offsets[i + 1] - offsets[i]). This call keeps,
+ * per peer, the longest prefix of its list in nearest-first order whose sizes sum to at most W_p.
+ *
+ * Inputs
+ *   - Rows, their clamping, overlapping rows and `error` bit 0 are as in wq_peer_budget_device: row p
+ *     is the part of [d_peer_offsets[p], d_peer_offsets[p + 1]) inside [0, n_in), and the rows are
+ *     walked up to n_in elements in total.
+ *   - Keys are as in wq_peer_budget_device: d2 = (dx*dx + dy*dy) + dz*dz in f64, no contraction;
+ *     +infinity for NaN, for m >= n_msgs (`error` bit 1) and for a peer without a position. Elements
+ *     order by (d2, position in the input row). Positions are resolved in the same way: the handle's
+ *     when d_peer_pos is NULL.
+ *   - The size of element j is d_msg_size[d_msgs[j]], a u32; it is 0, and nothing is read, when
+ *     d_msgs[j] >= n_msgs. d_msg_size[n_msgs] is required when n_msgs > 0 and never read outside
+ *     [0, n_msgs).
+ *   - W_p = d_budget_bytes[p] (u64 per peer), or w when d_budget_bytes is NULL.
+ * Output
+ *   - An element of row p is kept iff the sum of the sizes of all elements of row p at or before it in
+ *     the (d2, position) order, its own included, is <= W_p. The sum is taken in u64; a row has fewer
+ *     than 2^32 elements of less than 2^32 bytes each, so neither a row's total nor the call's wraps.
+ *   - So the kept set is a prefix of that order. W_p == 0 keeps exactly the leading zero-size
+ *     elements. If the nearest message alone exceeds W_p nothing behind it is kept either (zero-size
+ *     elements before it are): priority is strict, a far small message never overtakes a near large
+ *     one. A caller who must always send the head sets W_p at least to its largest frame. A row whose
+ *     total is <= W_p is copied.
+ *   - The output keeps input order (a stable compaction) and is deterministic byte for byte; nothing
+ *     is read back. d_out_offsets[0 .. n_peers] is always written in full, from 0.
+ *   - d_out_bytes (nullable): entry p is the kept bytes of row p, what a transport sizes its send
+ *     buffers from. d_counters is nullable.
+ *   - Nothing is written outside d_out_offsets[0 .. n_peers], d_out_msgs[0 .. n_kept),
+ *     d_out_bytes[0 .. n_peers) and the counters. Outputs must not alias inputs.
+ * Composition
+ *   - wq_peer_budget_device (count B) first and this call on its output keeps exactly the elements
+ *     with both "rank < B" and "running bytes <= W": a stable compaction preserves the elements'
+ *     relative positions, so the order of the survivors is the order they had, and the first cap keeps
+ *     a prefix of it. That is how a caller gets both caps; there is no combined entry point.
+ * Execution
+ *   - Asynchronous on the handle's stream. As the count budget, with a weighted radix select for rows
+ *     longer than 256 elements: its histograms sum sizes in u64 and each pass picks the bin in which
+ *     the running byte total first exceeds what is left of W_p. No lane, wave or block walks a row;
+ *     placement comes from counts and prefix sums, the atomics are integer adds.
+ *   - Scratch lives in the handle, grow-only, released with it: the count budget's buffers, shared
+ *     with it, plus at most 20.1 n_in + 2080 bytes of its own (size 4, one u64 scan 8, the select's u64
+ *     histograms 8 per element); together at most 38.1 n_in + 12 (n_peers + 1) bytes plus the scans'
+ *     (each buffer is allocated a quarter above its need). A steady-state call does no hipMalloc,
+ *     and the two budget calls may alternate on one handle.
+ * Limits and handle kinds
+ *   - As wq_peer_budget_device: n_in <= 2^32 - 1, n_peers < 2^32 - 1; the same WQ_E_INVALID cases
+ *     (d_msg_size NULL with n_msgs > 0 among the null arrays), nothing launched then; a multi-GPU
+ *     handle needs explicit positions and takes the arrays on devices[0]. */
+typedef struct wq_budget_bytes_counters {
+    uint64_t n_in;        /* elements inside the clamped input rows */
+    uint64_t n_kept;      /* elements written = out_offsets[n_peers] */
+    uint64_t bytes_in;    /* sum of the sizes of those n_in elements */
+    uint64_t bytes_kept;  /* sum of the sizes of the kept ones */
+    uint32_t rows_cut;    /* rows that lost at least one element */
+    uint32_t error;       /* bits 0 and 1 as in wq_budget_counters */
+} wq_budget_bytes_counters;
+int wq_peer_budget_bytes_device(wq_router* h,
+        const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
+        const double* d_msg_pos, const uint32_t* d_msg_size, size_t n_msgs,
+        const double* d_peer_pos, size_t n_peer_pos,
+        uint64_t w, const uint64_t* d_budget_bytes,
+        uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
+        wq_budget_bytes_counters* d_counters);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

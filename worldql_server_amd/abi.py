@@ -56,6 +56,10 @@ BUDGET_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_kept", np.uint64),
 BUDGET_ERROR_ROWS = 1      # wq_budget_counters.error bit 0: a row descended or reached past n_in
 BUDGET_ERROR_MSG = 2       # bit 1: a message index was >= n_msgs
 
+# struct wq_budget_bytes_counters: 40 bytes (wq_peer_budget_bytes_device); the error bits are the same
+BUDGET_BYTES_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_kept", np.uint64), ("bytes_in", np.uint64),
+                                        ("bytes_kept", np.uint64), ("rows_cut", np.uint32), ("error", np.uint32)])
+
 
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]

@@ -3,7 +3,8 @@
 // rule and u64 image, the class of a row, the rank of an element of a short row, the digit and match
 // tests of the radix select and the keep predicate. __host__ __device__, so
 // tests/cpp/peer_budget_host_shim.hip runs the same code on the CPU against
-// worldql_server_amd/interest.py (peer_budget_np).
+// worldql_server_amd/interest.py (peer_budget_np). The byte budgets' additions are at the end of the
+// file (tests/cpp/peer_budget_bytes_host_shim.hip, peer_budget_bytes_np).
 //
 // Ordinals. Row p is the part of [off[p], off[p + 1]) inside [0, n_in) (pm_row_bounds). The rows'
 // lengths are summed with a saturating add and the sums clamped to n_in: row p owns the ordinals
@@ -172,6 +173,75 @@ __host__ __device__ __forceinline__ uint32_t bud_before(const uint32_t* __restri
 #else
     return base[x >> 6] + (uint32_t)__builtin_popcountll(below);
 #endif
+}
+
+// ---- byte budgets (wq_peer_budget_bytes_device): the same ordinal space, keys, classes of cut rows
+// and flag words; the select sums sizes where the count budget counts keys. An element is kept iff
+// the sizes of the row's elements at or before it in (key, position) order sum to at most W, in u64:
+// a row has fewer than 2^32 elements of less than 2^32 bytes each, so no sum wraps.
+
+// The weighted select's state of one long cut row: the digits chosen so far and the bytes still free
+// for the keys that match them. After the last pass: the row's threshold key and the bytes left for
+// the elements with exactly that key.
+struct BudSelW {
+    uint64_t prefix;
+    uint64_t remaining;
+    uint32_t active;
+    uint32_t pad;
+};
+
+__host__ __device__ __forceinline__ uint64_t bud_wbudget(const uint64_t* __restrict__ budget, uint64_t w, uint32_t p) {
+    return budget ? budget[p] : w;
+}
+
+// Size of the element with message m: 0, without a read, when the message does not exist.
+__host__ __device__ __forceinline__ uint32_t bud_size(const uint32_t* __restrict__ msize, uint32_t n_msgs, uint32_t m) {
+    return m < n_msgs ? msize[m] : 0u;
+}
+
+// A row whose total fits is copied; a cut one is decided by summing in the row (short) or by the
+// weighted select (long). A cut row loses at least its last element in (key, position) order.
+__host__ __device__ __forceinline__ uint8_t bud_class_bytes(uint32_t len, uint64_t total, uint64_t W) {
+    if (total <= W) return kBudAll;
+    return len <= kBudShort ? kBudShortCut : kBudLongCut;
+}
+
+// The term of ordinal q in a scan of bytes over the ordinals: its size, 0 behind the T ordinals and,
+// with flag words, 0 when its flag is not set.
+__host__ __device__ __forceinline__ uint64_t bud_byte_term(const uint32_t* __restrict__ size,
+                                                           const uint64_t* __restrict__ words, uint32_t T,
+                                                           uint64_t q) {
+    if (q >= T) return 0;
+    if (words && !((words[q >> 6] >> (q & 63u)) & 1ull)) return 0;
+    return size[q];
+}
+
+// Short cut row [q0, q0 + len): do the sizes of the elements not after ordinal q in (key, position)
+// order, its own included, fit in W?
+__host__ __device__ __forceinline__ bool bud_short_keeps_bytes(const uint64_t* __restrict__ key,
+                                                               const uint32_t* __restrict__ size, uint32_t q0,
+                                                               uint32_t len, uint32_t q, uint64_t W) {
+    const uint64_t mine = key[q];
+    uint64_t sum = 0;
+    for (uint32_t i = q0; i < q0 + len; ++i) {
+        const uint64_t o = key[i];
+        sum += (o < mine || (o == mine && i <= q)) ? (uint64_t)size[i] : 0ull;
+    }
+    return sum <= W;
+}
+
+// The bin in which the running byte total first exceeds `remaining`: below = the bytes of the
+// matching keys in lower bins. A cut row's matching bytes exceed `remaining`, so exactly one bin is
+// picked; bins of zero-size elements are never picked.
+__host__ __device__ __forceinline__ bool bud_picks_bytes(uint64_t below, uint64_t bytes, uint64_t remaining) {
+    return below <= remaining && remaining - below < bytes;
+}
+
+// Long cut row after the weighted select: kept below the threshold key, and at it while the bytes of
+// the row's threshold-key elements up to and including this one (tie_bytes) fit in thr_bytes.
+__host__ __device__ __forceinline__ bool bud_keeps_bytes(uint64_t key, uint64_t tie_bytes, uint64_t thr_key,
+                                                         uint64_t thr_bytes) {
+    return key < thr_key || (key == thr_key && tie_bytes <= thr_bytes);
 }
 
 }  // namespace wq

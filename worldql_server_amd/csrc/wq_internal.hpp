@@ -251,6 +251,11 @@ struct wq_router {
     wq::DevBuf bud_len, bud_sum, bud_pre, bud_key, bud_row, bud_cls, bud_sel, bud_hist, bud_words, bud_cnt, bud_base,
         bud_ctrl;
     size_t bud_hist_clean = 0;  // bytes of bud_hist known to be zero (0: clear before the next select)
+    // byte budgets (wq_budget.hip): they run on the buffers above and add, per ordinal, the size and
+    // one u64 scan entry, and per slot the weighted select's state and u64 histogram, zero between
+    // calls under a clean-byte count of its own, so the two calls alternate on one handle
+    wq::DevBuf byt_size, byt_scan, byt_sel, byt_hist;
+    size_t byt_hist_clean = 0;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -354,6 +359,11 @@ int launch_peer_budget(wq_router* h, const uint32_t* d_peer_offsets, const uint3
                        size_t n_in, const double* d_msg_pos, size_t n_msgs, const double* d_peer_pos,
                        size_t n_peer_pos, uint32_t k, const uint32_t* d_budget, uint32_t* d_out_offsets,
                        uint32_t* d_out_msgs, wq_budget_counters* d_counters);
+int launch_peer_budget_bytes(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
+                             size_t n_in, const double* d_msg_pos, const uint32_t* d_msg_size, size_t n_msgs,
+                             const double* d_peer_pos, size_t n_peer_pos, uint64_t w, const uint64_t* d_budget_bytes,
+                             uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
+                             wq_budget_bytes_counters* d_counters);
 void budget_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);

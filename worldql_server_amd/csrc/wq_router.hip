@@ -701,6 +701,30 @@ int wq_peer_budget_device(wq_router* h, const uint32_t* d_peer_offsets, const ui
                               d_budget, d_out_offsets, d_out_msgs, d_counters);
 }
 
+int wq_peer_budget_bytes_device(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs,
+                                uint32_t n_peers, size_t n_in, const double* d_msg_pos, const uint32_t* d_msg_size,
+                                size_t n_msgs, const double* d_peer_pos, size_t n_peer_pos, uint64_t w,
+                                const uint64_t* d_budget_bytes, uint32_t* d_out_offsets, uint32_t* d_out_msgs,
+                                uint64_t* d_out_bytes, wq_budget_bytes_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!d_out_offsets || (n_peers && !d_peer_offsets) || (n_in && (!d_msgs || !d_out_msgs)) ||
+        (n_msgs && (!d_msg_pos || !d_msg_size)) || (!d_peer_pos && n_peer_pos))
+        return set_error(h, WQ_E_INVALID, "peer_budget_bytes: a null array with a non-zero size");
+    if (n_in > 0xFFFFFFFFull || n_peers == 0xFFFFFFFFu)
+        return set_error(h, WQ_E_INVALID, "peer_budget_bytes: n_in must be <= 2^32 - 1 and n_peers < 2^32 - 1");
+    if (!d_peer_pos) {
+        if (h->multi)
+            return set_error(h, WQ_E_INVALID, "peer_budget_bytes: a multi-GPU handle needs explicit peer positions");
+        if (!h->n_ppos)
+            return set_error(h, WQ_E_INVALID, "peer_budget_bytes: no peer positions (wq_set_peer_positions)");
+        d_peer_pos = h->ppos.as<double>();
+        n_peer_pos = h->n_ppos;
+    }
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_peer_budget_bytes(h, d_peer_offsets, d_msgs, n_peers, n_in, d_msg_pos, d_msg_size, n_msgs, d_peer_pos,
+                                    n_peer_pos, w, d_budget_bytes, d_out_offsets, d_out_msgs, d_out_bytes, d_counters);
+}
+
 // The argument rules both forms of wq_csr_diff share (capacities already clamped to 2^32 - 1).
 static bool csr_diff_args_ok(const uint32_t* old_off, const uint32_t* old_peers, size_t old_cap, const uint32_t* new_off,
                              const uint32_t* new_peers, size_t new_cap, const uint32_t* ent_off,

@@ -9,6 +9,8 @@ observers that entered and left every entity's interest set since the previous t
 `peer_major_np` is the definition of the per-peer send lists (wq_peer_major_device) and
 `peer_budget_np` the definition of the send budgets that follow them (wq_peer_budget_device,
 csrc/wq_budget.hip): of every peer's list the min(budget, len) messages nearest to the peer.
+`peer_budget_bytes_np` is the definition of the byte budgets (wq_peer_budget_bytes_device): of every
+peer's list the nearest messages whose sizes sum to at most the peer's bytes.
 """
 from __future__ import annotations
 
@@ -186,6 +188,73 @@ def peer_budget_np(peer_offsets, msgs, msg_pos, peer_pos, k=None, budget=None):
     return out_off, out_msgs, dict(n_in=walked, n_kept=int(out_off[-1]), rows_cut=rows_cut, error=error)
 
 
+def frame_sizes(offsets):
+    """The u32 size of every frame from wq_serialize_messages' u64 offsets[n + 1], the msg_size array of
+    the byte budgets. Raises on a frame of 2^32 bytes or more (the codec's own limit is 2 GiB)."""
+    sizes = np.diff(np.ascontiguousarray(offsets, dtype=np.uint64))
+    if len(sizes) and int(sizes.max()) >= 1 << 32:
+        raise ValueError("a frame of 2^32 bytes or more has no u32 size")
+    return sizes.astype(np.uint32)
+
+
+def peer_budget_bytes_np(peer_offsets, msgs, msg_pos, msg_size, peer_pos, w=None, budget=None):
+    """Byte budgets, the definition of what wq_peer_budget_bytes_device writes: an element of row p is
+    kept iff the sizes of all elements of row p at or before it in the (d2, position) order, its own
+    included, sum to at most W_p (budget[p], or w for everyone), so each row keeps a prefix of that
+    order; the kept elements stay in input order. Returns (out_offsets[n_peers + 1], out_msgs[n_kept],
+    out_bytes[n_peers] u64, counters) with counters a dict of n_in, n_kept, bytes_in, bytes_kept,
+    rows_cut, error.
+
+    Rows, keys and the error bits are peer_budget_np's. The size of an element with message m is
+    msg_size[m], and 0 when m >= len(msg_pos). The sums are Python ints. Row by row, for clarity."""
+    off = np.ascontiguousarray(peer_offsets, dtype=np.uint32).astype(np.int64)
+    msgs = np.ascontiguousarray(msgs, dtype=np.uint32)
+    msg_pos = np.ascontiguousarray(msg_pos, dtype=np.float64).reshape(-1, 3)
+    msg_size = np.ascontiguousarray(msg_size, dtype=np.uint32)
+    peer_pos = np.ascontiguousarray(peer_pos, dtype=np.float64).reshape(-1, 3)
+    n_in, n_peers, n_msgs = len(msgs), max(len(off) - 1, 0), len(msg_pos)
+    if budget is None and w is None:
+        raise ValueError("give w or a per-peer byte budget")
+    if len(msg_size) < n_msgs:
+        raise ValueError("msg_size needs an entry per message")
+    out_off = np.zeros(n_peers + 1, dtype=np.uint32)
+    out_bytes = np.zeros(n_peers, dtype=np.uint64)
+    out, walked, rows_cut, error, bytes_in = [], 0, 0, 0, 0
+    for p in range(n_peers):
+        a, b = min(off[p], n_in), min(off[p + 1], n_in)
+        b = max(a, b)
+        if off[p] > off[p + 1] or off[p + 1] > n_in:
+            error |= 1
+        n = min(b - a, n_in - walked)
+        if n != b - a:
+            error |= 1
+        walked += n
+        row = msgs[a:a + n]
+        W = int(budget[p]) if budget is not None else int(w)
+        if (row.astype(np.int64) >= n_msgs).any():
+            error |= 2
+        sizes = [int(msg_size[m]) if m < n_msgs else 0 for m in row.tolist()]
+        bytes_in += sum(sizes)
+        d2 = budget_keys_np(row, msg_pos, peer_pos, p)
+        order = np.lexsort((np.arange(n), d2)).tolist()    # by d2, then position
+        kept, running = [], 0
+        for i in order:
+            running += sizes[i]
+            if running > W:
+                break                                       # everything behind it has a larger sum
+            kept.append(i)
+        if len(kept) < n:
+            rows_cut += 1
+        kept.sort()                                         # back in input order
+        out.append(row[kept] if kept else row[:0])
+        out_off[p + 1] = out_off[p] + len(kept)
+        out_bytes[p] = sum(sizes[i] for i in kept)
+    out_msgs = np.concatenate(out).astype(np.uint32) if out else np.zeros(0, np.uint32)
+    return out_off, out_msgs, out_bytes, dict(n_in=walked, n_kept=int(out_off[-1]), bytes_in=bytes_in,
+                                              bytes_kept=int(sum(int(v) for v in out_bytes)), rows_cut=rows_cut,
+                                              error=error)
+
+
 class InterestTracker:
     """Routes ticks of `n_rows` entities (row m of every tick = entity m) and keeps the previous
     tick's CSR on the device, so every `route` also returns who entered and who left each row.
@@ -306,3 +375,26 @@ class InterestTracker:
         torch.cuda.synchronize(self.dev)
         kept = int(oo[n_peers].item()) & 0xFFFFFFFF
         return oo, om[:kept]
+
+    def peer_budget_bytes(self, peer_offsets, rows, msg_pos_ptr: int, msg_size_ptr: int, w: int | None = None,
+                          budget_bytes_ptr: int | None = None, peer_pos_ptr: int | None = None, n_peer_pos: int = 0):
+        """Chains after peer_major or peer_budget: of every observer's list the nearest entities whose
+        sizes (msg_size_ptr: u32 per entity on the device, see frame_sizes) sum to at most its byte
+        budget (budget_bytes_ptr: u64 per observer, else w for everyone), in input order, through
+        wq_peer_budget_bytes_device: (out_offsets[n_peers + 1], out_rows[kept], out_bytes[n_peers]), the
+        last an int64 tensor of every observer's kept bytes. Positions as in peer_budget."""
+        torch = self.torch
+        if w is None and budget_bytes_ptr is None:
+            raise ValueError("give w or budget_bytes_ptr")
+        n_peers, n_in = peer_offsets.numel() - 1, rows.numel()
+        oo = torch.empty(n_peers + 1, dtype=torch.int32, device=self.dev)
+        om = torch.empty(max(n_in, 1), dtype=torch.int32, device=self.dev)
+        ob = torch.empty(max(n_peers, 1), dtype=torch.int64, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self.router.peer_budget_bytes_device(peer_offsets.data_ptr(), rows.data_ptr() if n_in else None, n_peers, n_in,
+                                             msg_pos_ptr, msg_size_ptr, self.n_rows, peer_pos_ptr, n_peer_pos, w or 0,
+                                             budget_bytes_ptr, oo.data_ptr(), om.data_ptr() if n_in else None,
+                                             ob.data_ptr(), None)
+        torch.cuda.synchronize(self.dev)
+        kept = int(oo[n_peers].item()) & 0xFFFFFFFF
+        return oo, om[:kept], ob[:n_peers]

@@ -78,6 +78,8 @@ def load_library(build_if_missing: bool = True):
         "wq_route_global_device": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, vp], i32),
         "wq_peer_major_device": ([vp, vp, vp, sz, sz, vp, u32, vp, vp], i32),
         "wq_peer_budget_device": ([vp, vp, vp, u32, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp], i32),
+        "wq_peer_budget_bytes_device": ([vp, vp, vp, u32, sz, vp, vp, sz, vp, sz, ctypes.c_uint64, vp, vp, vp, vp, vp],
+                                        i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -390,6 +392,22 @@ class Router:
                                                    msg_pos_ptr or None, n_msgs, peer_pos_ptr or None, n_peer_pos, k,
                                                    budget_ptr or None, out_offsets_ptr or None, out_msgs_ptr or None,
                                                    counters_ptr or None))
+
+    def peer_budget_bytes_device(self, peer_offsets_ptr: int | None, msgs_ptr: int | None, n_peers: int, n_in: int,
+                                 msg_pos_ptr: int | None, msg_size_ptr: int | None, n_msgs: int,
+                                 peer_pos_ptr: int | None, n_peer_pos: int, w: int, budget_bytes_ptr: int | None,
+                                 out_offsets_ptr: int | None, out_msgs_ptr: int | None,
+                                 out_bytes_ptr: int | None = None, counters_ptr: int | None = None) -> None:
+        """wq_peer_budget_bytes_device: of every row of a peer-major CSR the nearest messages whose sizes
+        (msg_size_ptr: u32 per message) sum to at most the peer's byte budget (budget_bytes_ptr: u64 per
+        peer, else w for everyone), in input order; asynchronous on the handle's stream. out_bytes_ptr
+        (u64 per peer, optional) receives every row's kept bytes; the counters
+        (abi.BUDGET_BYTES_COUNTERS_DTYPE) stay where counters_ptr points. Host definition:
+        interest.peer_budget_bytes_np."""
+        self._check(self.lib.wq_peer_budget_bytes_device(
+            self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in, msg_pos_ptr or None, msg_size_ptr or None,
+            n_msgs, peer_pos_ptr or None, n_peer_pos, w, budget_bytes_ptr or None, out_offsets_ptr or None,
+            out_msgs_ptr or None, out_bytes_ptr or None, counters_ptr or None))
 
     # ---- interest changes between two ticks (include/wq_router.h; host reference: interest.py) ----
     def csr_diff(self, old_offsets, old_peers, new_offsets, new_peers, with_left: bool = True,
