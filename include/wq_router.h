@@ -810,6 +810,92 @@ int wq_peer_budget_bytes_device(wq_router* h,
         uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
         wq_budget_bytes_counters* d_counters);
 
+/* ---- send buffers: every peer's frames packed into one contiguous byte run ----
+ * The budgets leave, per peer, a list of message indices, and wq_serialize_messages leaves the tick's
+ * frames in one array (frame i is out[offsets[i] .. offsets[i + 1])). This call does the fan-out on
+ * the device: for every peer the frames of its list, in list order, in one byte run that a transport
+ * hands to a socket with one write. An extension like the budgets: the reference has no batching
+ * transport, its broadcast_to! (transport/peer_map.rs:22-40) clones the bytes and calls send_raw
+ * once per recipient.
+ *
+ * Rows
+ *   - d_peer_offsets[n_peers + 1] / d_msgs[n_in] are any peer-major CSR: wq_peer_major_device's,
+ *     either budget's, or the transposed output of wq_csr_diff.
+ *   - Rows, their clamping to [0, n_in), the walk of at most n_in elements in total and `error` bit 0
+ *     are exactly wq_peer_budget_device's.
+ *   - Ordinal q is the q-th walked element. For offsets that ascend from 0 without gaps, which is
+ *     every CSR this library writes, q equals the index into d_msgs.
+ * Frames
+ *   - The frame of the element with message m = d_msgs[j] is d_frames[fo[m] .. fo[m + 1]), with
+ *     fo = d_frame_offsets[n_msgs + 1].
+ *   - The frame is taken as empty (size 0, nothing read from d_frames) when m >= n_msgs (`error` bit 1,
+ *     fo is not read), and when fo[m] > fo[m + 1], fo[m + 1] > n_frame_bytes or
+ *     fo[m + 1] - fo[m] >= 2^32 (`error` bit 2). Only frames that an element references are looked at.
+ *   - A frame is whole or empty, never truncated. d_frames may have any alignment.
+ *   - Nothing is dereferenced outside [0, n_in), [0, n_peers], [0, n_msgs] of fo and
+ *     [0, n_frame_bytes) of d_frames, whatever the arrays hold.
+ * Records and output layout
+ *   - The record of an element is the optional 4-byte prefix (flags & WQ_PACK_LEN_PREFIX: the frame's
+ *     size as a u32, little endian) followed by the frame. With the prefix on, an empty frame is
+ *     still a 4-byte record holding 0.
+ *   - E[q] is the exclusive u64 prefix sum of the record sizes over the ordinals. Record q occupies
+ *     d_out[E[q] .. E[q] + rec_q).
+ *   - Peer p's run is d_out[PB[p] .. PB[p + 1]), PB[p] = E[first ordinal of row p] and
+ *     PB[n_peers] = bytes_need. Without the prefix, after wq_peer_budget_bytes_device,
+ *     PB[p + 1] - PB[p] is that call's d_out_bytes[p].
+ *   - d_out_peer_bytes is PB, always written in full, from 0 and uncut, including n_in == 0 and
+ *     n_peers == 0.
+ *   - d_out_elem_bytes[q] = E[q] for every walked ordinal (nullable): the record boundaries, for a
+ *     transport that sends frame by frame.
+ * Capacity
+ *   - Bytes at positions >= capacity_bytes are not written, as wq_csr_diff_device does with pairs;
+ *     everything below is exact, so a peer with PB[p + 1] <= capacity_bytes has its whole run. A cut
+ *     may fall inside a prefix or inside a frame. `overflow` and bytes_need tell the caller to grow.
+ *   - d_out == NULL with capacity_bytes == 0 is the sizing call: offsets and counters only.
+ * Output guarantees
+ *   - Nothing is written outside d_out[0 .. bytes_written), d_out_peer_bytes[0 .. n_peers],
+ *     d_out_elem_bytes[0 .. n_in walked) and the counters. Outputs must not alias inputs.
+ *   - The output is deterministic byte for byte: placement comes from scans, and the only atomics are
+ *     ORs into the error word.
+ *   - d_out must be 16-byte aligned (every hipMalloc result is).
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. The copy's grid is sized from
+ *     capacity_bytes and walks the output bytes: a wave owns 1 KiB of output and a lane 16 bytes, so
+ *     no lane, wave or block owns a row or a frame.
+ *   - Scratch lives in the handle, grow-only: at most 20 n_in + 8 + 12 (n_peers + 1) bytes (per
+ *     ordinal the frame's size 4, its start 8 and E 8; the rows' three words, shared with the
+ *     budgets) plus the scans' (each buffer is allocated a quarter above its need). A steady-state
+ *     call does no hipMalloc, and the call may alternate freely with both budget calls on one handle.
+ * Limits and handle kinds
+ *   - WQ_E_INVALID, with nothing launched, for a null handle, a null required array with a non-zero
+ *     size (d_out_peer_bytes is always required), d_out == NULL with capacity_bytes > 0, a misaligned
+ *     d_out, unknown flag bits, n_in > 2^32 - 1 and n_peers >= 2^32 - 1.
+ *   - Like wq_peer_major_device the call needs only a stream and scratch: a multi-GPU handle runs it
+ *     on its own stream with the arrays on devices[0].
+ *   - Packing into mapped host memory is not covered here and has not been measured. */
+#define WQ_PACK_LEN_PREFIX 1u   /* every frame is preceded by its size as a u32, little endian */
+
+typedef struct wq_pack_counters {
+    uint64_t n_in;          /* elements inside the clamped input rows (the ordinals walked) */
+    uint64_t n_complete;    /* elements whose whole record lies below capacity_bytes */
+    uint64_t bytes_need;    /* bytes of the whole result = d_out_peer_bytes[n_peers] */
+    uint64_t bytes_written; /* min(bytes_need, capacity_bytes) */
+    uint32_t overflow;      /* bit 0: bytes_need > capacity_bytes */
+    uint32_t error;         /* bit 0: a row descended or reached past n_in;
+                               bit 1: a message index was >= n_msgs;
+                               bit 2: a referenced frame's offsets descend, reach past
+                                      n_frame_bytes or span 2^32 bytes or more */
+} wq_pack_counters;         /* 40 bytes */
+
+int wq_peer_pack_device(wq_router* h,
+        const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
+        const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_msgs, size_t n_frame_bytes,
+        uint32_t flags,
+        uint8_t* d_out, size_t capacity_bytes,
+        uint64_t* d_out_peer_bytes,   /* [n_peers + 1], required */
+        uint64_t* d_out_elem_bytes,   /* [n_in], nullable */
+        wq_pack_counters* d_counters  /* nullable */);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

@@ -60,6 +60,14 @@ BUDGET_ERROR_MSG = 2       # bit 1: a message index was >= n_msgs
 BUDGET_BYTES_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_kept", np.uint64), ("bytes_in", np.uint64),
                                         ("bytes_kept", np.uint64), ("rows_cut", np.uint32), ("error", np.uint32)])
 
+# struct wq_pack_counters: 40 bytes (wq_peer_pack_device)
+PACK_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_complete", np.uint64), ("bytes_need", np.uint64),
+                                ("bytes_written", np.uint64), ("overflow", np.uint32), ("error", np.uint32)])
+PACK_LEN_PREFIX = 1        # WQ_PACK_LEN_PREFIX: every frame is preceded by its size as a u32, little endian
+PACK_ERROR_ROWS = 1        # wq_pack_counters.error bit 0: a row descended or reached past n_in
+PACK_ERROR_MSG = 2         # bit 1: a message index was >= n_msgs
+PACK_ERROR_FRAME = 4       # bit 2: a referenced frame's offsets descend, reach past n_frame_bytes or span >= 2^32
+
 
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]

@@ -256,6 +256,9 @@ struct wq_router {
     // calls under a clean-byte count of its own, so the two calls alternate on one handle
     wq::DevBuf byt_size, byt_scan, byt_sel, byt_hist;
     size_t byt_hist_clean = 0;
+    // send buffers (wq_pack.hip): the rows run on bud_len / bud_sum / bud_pre above; per ordinal the
+    // frame's size, where it starts and one u64 scan entry; {unused, error}
+    wq::DevBuf pack_size, pack_src, pack_scan, pack_ctrl;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -365,6 +368,12 @@ int launch_peer_budget_bytes(wq_router* h, const uint32_t* d_peer_offsets, const
                              uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
                              wq_budget_bytes_counters* d_counters);
 void budget_release(wq_router* h);
+// wq_pack.hip: the send buffers on device arrays (asynchronous), and its scratch's release.
+int launch_peer_pack(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
+                     const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_msgs, size_t n_frame_bytes,
+                     uint32_t flags, uint8_t* d_out, size_t capacity_bytes, uint64_t* d_out_peer_bytes,
+                     uint64_t* d_out_elem_bytes, wq_pack_counters* d_counters);
+void pack_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
 // wq_table_export.hip: frees the export's scratch.

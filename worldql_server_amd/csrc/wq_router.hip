@@ -126,6 +126,7 @@ int wq_router_destroy(wq_router* h) {
     follow_release(h);
     csr_diff_release(h);
     budget_release(h);
+    pack_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -723,6 +724,24 @@ int wq_peer_budget_bytes_device(wq_router* h, const uint32_t* d_peer_offsets, co
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_peer_budget_bytes(h, d_peer_offsets, d_msgs, n_peers, n_in, d_msg_pos, d_msg_size, n_msgs, d_peer_pos,
                                     n_peer_pos, w, d_budget_bytes, d_out_offsets, d_out_msgs, d_out_bytes, d_counters);
+}
+
+int wq_peer_pack_device(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
+                        size_t n_in, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_msgs,
+                        size_t n_frame_bytes, uint32_t flags, uint8_t* d_out, size_t capacity_bytes,
+                        uint64_t* d_out_peer_bytes, uint64_t* d_out_elem_bytes, wq_pack_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!d_out_peer_bytes || (n_peers && !d_peer_offsets) || (n_in && !d_msgs) || (n_msgs && !d_frame_offsets) ||
+        (n_frame_bytes && !d_frames))
+        return set_error(h, WQ_E_INVALID, "peer_pack: a null array with a non-zero size");
+    if (!d_out && capacity_bytes) return set_error(h, WQ_E_INVALID, "peer_pack: capacity_bytes without d_out");
+    if ((uintptr_t)d_out & 15u) return set_error(h, WQ_E_INVALID, "peer_pack: d_out must be 16-byte aligned");
+    if (flags & ~(uint32_t)WQ_PACK_LEN_PREFIX) return set_error(h, WQ_E_INVALID, "peer_pack: unknown flag bits");
+    if (n_in > 0xFFFFFFFFull || n_peers == 0xFFFFFFFFu)
+        return set_error(h, WQ_E_INVALID, "peer_pack: n_in must be <= 2^32 - 1 and n_peers < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_peer_pack(h, d_peer_offsets, d_msgs, n_peers, n_in, d_frames, d_frame_offsets, n_msgs, n_frame_bytes,
+                            flags, d_out, capacity_bytes, d_out_peer_bytes, d_out_elem_bytes, d_counters);
 }
 
 // The argument rules both forms of wq_csr_diff share (capacities already clamped to 2^32 - 1).

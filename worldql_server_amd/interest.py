@@ -11,6 +11,8 @@ observers that entered and left every entity's interest set since the previous t
 csrc/wq_budget.hip): of every peer's list the min(budget, len) messages nearest to the peer.
 `peer_budget_bytes_np` is the definition of the byte budgets (wq_peer_budget_bytes_device): of every
 peer's list the nearest messages whose sizes sum to at most the peer's bytes.
+`peer_pack_np` is the definition of the send buffers (wq_peer_pack_device, csrc/wq_pack.hip): every
+peer's frames in one contiguous byte run, in list order.
 """
 from __future__ import annotations
 
@@ -255,6 +257,59 @@ def peer_budget_bytes_np(peer_offsets, msgs, msg_pos, msg_size, peer_pos, w=None
                                               error=error)
 
 
+def peer_pack_np(peer_offsets, msgs, frames, frame_offsets, len_prefix=False, capacity=None):
+    """Send buffers, the definition of what wq_peer_pack_device writes: for every row of the peer-major
+    CSR (peer_offsets[n_peers + 1], msgs[n_in]) the records of its elements, in list order, in one byte
+    run. Returns (out_bytes u8[bytes_written], peer_bytes u64[n_peers + 1], elem_bytes u64[walked],
+    counters) with counters a dict of n_in, n_complete, bytes_need, bytes_written, overflow, error.
+
+    Rows and error bit 0 are peer_budget_np's: row p is the part of [peer_offsets[p],
+    peer_offsets[p + 1]) inside [0, n_in), and the rows are walked up to n_in elements in total. The
+    frame of an element with message m is frames[fo[m]:fo[m + 1]], fo = frame_offsets[n_msgs + 1]; it is
+    empty when m >= n_msgs (error bit 1) and when fo[m] > fo[m + 1], fo[m + 1] > len(frames) or the
+    frame spans 2^32 bytes or more (error bit 2). A record is the frame, behind its size as a
+    little-endian u32 with len_prefix. elem_bytes[q] is where the record of the q-th walked element
+    starts and peer_bytes[p] where row p's first record does; peer_bytes[n_peers] = bytes_need. Only
+    the first `capacity` bytes are written (None: all of them); n_complete counts the records that lie
+    wholly below it. Row by row, for clarity."""
+    off = np.ascontiguousarray(peer_offsets, dtype=np.uint32).astype(np.int64)
+    msgs = np.ascontiguousarray(msgs, dtype=np.uint32)
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    fo = [int(v) for v in np.ascontiguousarray(frame_offsets, dtype=np.uint64)]
+    n_in, n_peers, n_msgs, n_frame_bytes = len(msgs), max(len(off) - 1, 0), max(len(fo) - 1, 0), len(frames)
+    peer_bytes = np.zeros(n_peers + 1, dtype=np.uint64)
+    records, elem_bytes, walked, error, at = [], [], 0, 0, 0
+    for p in range(n_peers):
+        a, b = min(off[p], n_in), min(off[p + 1], n_in)
+        b = max(a, b)
+        if off[p] > off[p + 1] or off[p + 1] > n_in:
+            error |= 1
+        n = min(b - a, n_in - walked)
+        if n != b - a:
+            error |= 1
+        walked += n
+        peer_bytes[p] = at
+        for m in msgs[a:a + n].tolist():
+            frame = b""
+            if m >= n_msgs:
+                error |= 2
+            elif fo[m] > fo[m + 1] or fo[m + 1] > n_frame_bytes or fo[m + 1] - fo[m] >= 1 << 32:
+                error |= 4
+            else:
+                frame = frames[fo[m]:fo[m + 1]].tobytes()
+            record = (len(frame).to_bytes(4, "little") if len_prefix else b"") + frame
+            elem_bytes.append(at)
+            records.append(record)
+            at += len(record)
+    peer_bytes[n_peers] = at
+    cap = at if capacity is None else int(capacity)
+    written = min(at, cap)
+    out = np.frombuffer(b"".join(records)[:written], dtype=np.uint8).copy()
+    n_complete = sum(1 for e, r in zip(elem_bytes, records) if e + len(r) <= cap)
+    return out, peer_bytes, np.array(elem_bytes, dtype=np.uint64), dict(
+        n_in=walked, n_complete=n_complete, bytes_need=at, bytes_written=written, overflow=int(at > cap), error=error)
+
+
 class InterestTracker:
     """Routes ticks of `n_rows` entities (row m of every tick = entity m) and keeps the previous
     tick's CSR on the device, so every `route` also returns who entered and who left each row.
@@ -282,6 +337,8 @@ class InterestTracker:
         self.left = [torch.zeros(self.n_rows + 1, **i32), torch.empty(cap, **i32), 0] if with_left else None
         self.route_cnt = torch.zeros(24, dtype=torch.uint8, device=self.dev)
         self.diff_cnt = torch.zeros(24, dtype=torch.uint8, device=self.dev)
+        self.pack_cnt = torch.zeros(40, dtype=torch.uint8, device=self.dev)
+        self.pack_buf = None  # peer_pack's send buffer, grow-only
         torch.cuda.synchronize(self.dev)
         self.ticks = 0
 
@@ -398,3 +455,35 @@ class InterestTracker:
         torch.cuda.synchronize(self.dev)
         kept = int(oo[n_peers].item()) & 0xFFFFFFFF
         return oo, om[:kept], ob[:n_peers]
+
+    def peer_pack(self, peer_offsets, rows, frames_ptr: int, frame_offsets_ptr: int, n_frame_bytes: int,
+                  len_prefix: bool = False):
+        """Chains after peer_major or either budget: every observer's frames in one contiguous byte run,
+        in list order, through wq_peer_pack_device: (out[bytes_need] uint8, peer_bytes[n_peers + 1],
+        elem_bytes[n_in]), the last two int64 tensors; observer p's run is out[peer_bytes[p]:
+        peer_bytes[p + 1]] and the record of list element q starts at elem_bytes[q]. frames_ptr /
+        frame_offsets_ptr: the tick's frames on the device as wq_serialize_messages leaves them (u8 bytes,
+        u64 offsets[n_rows + 1]), uploaded once per tick. `out` is a view of the tracker's grow-only
+        buffer, valid until the next call; a buffer that is too small is grown to bytes_need and the call
+        made once more."""
+        torch = self.torch
+        n_peers, n_in = peer_offsets.numel() - 1, rows.numel()
+        if self.pack_buf is None:
+            self.pack_buf = torch.empty(1 << 20, dtype=torch.uint8, device=self.dev)
+        pb = torch.empty(n_peers + 1, dtype=torch.int64, device=self.dev)
+        eb = torch.empty(max(n_in, 1), dtype=torch.int64, device=self.dev)
+        flags = abi.PACK_LEN_PREFIX if len_prefix else 0
+        for _ in range(2):
+            torch.cuda.synchronize(self.dev)
+            self.router.peer_pack_device(peer_offsets.data_ptr(), rows.data_ptr() if n_in else None, n_peers, n_in,
+                                         frames_ptr, frame_offsets_ptr, self.n_rows, n_frame_bytes, flags,
+                                         self.pack_buf.data_ptr(), self.pack_buf.numel(), pb.data_ptr(),
+                                         eb.data_ptr() if n_in else None, self.pack_cnt.data_ptr())
+            c = self._read(self.pack_cnt, abi.PACK_COUNTERS_DTYPE)
+            if not c["overflow"]:
+                break
+            need = int(c["bytes_need"])
+            self.pack_buf = torch.empty(need + need // 4, dtype=torch.uint8, device=self.dev)
+        if c["error"]:
+            raise RuntimeError(f"peer_pack error bits {int(c['error']):#x}")
+        return self.pack_buf[: int(c["bytes_written"])], pb, eb[: int(c["n_in"])]

@@ -80,6 +80,7 @@ def load_library(build_if_missing: bool = True):
         "wq_peer_budget_device": ([vp, vp, vp, u32, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp], i32),
         "wq_peer_budget_bytes_device": ([vp, vp, vp, u32, sz, vp, vp, sz, vp, sz, ctypes.c_uint64, vp, vp, vp, vp, vp],
                                         i32),
+        "wq_peer_pack_device": ([vp, vp, vp, u32, sz, vp, vp, sz, sz, u32, vp, sz, vp, vp, vp], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -408,6 +409,22 @@ class Router:
             self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in, msg_pos_ptr or None, msg_size_ptr or None,
             n_msgs, peer_pos_ptr or None, n_peer_pos, w, budget_bytes_ptr or None, out_offsets_ptr or None,
             out_msgs_ptr or None, out_bytes_ptr or None, counters_ptr or None))
+
+    def peer_pack_device(self, peer_offsets_ptr: int | None, msgs_ptr: int | None, n_peers: int, n_in: int,
+                         frames_ptr: int | None, frame_offsets_ptr: int | None, n_msgs: int, n_frame_bytes: int,
+                         flags: int, out_ptr: int | None, capacity_bytes: int, out_peer_bytes_ptr: int | None,
+                         out_elem_bytes_ptr: int | None = None, counters_ptr: int | None = None) -> None:
+        """wq_peer_pack_device: for every row of a peer-major CSR the frames of its messages
+        (frames_ptr[frame_offsets[m] .. frame_offsets[m + 1]), u64 offsets) in one contiguous byte run
+        of out_ptr, in list order, each behind its u32 size with flags = abi.PACK_LEN_PREFIX;
+        asynchronous on the handle's stream. out_peer_bytes_ptr (u64[n_peers + 1]) receives where every
+        peer's run starts, out_elem_bytes_ptr (u64[n_in], optional) where every record starts; the
+        counters (abi.PACK_COUNTERS_DTYPE) stay where counters_ptr points. out_ptr None with capacity 0
+        sizes the buffer. Host definition: interest.peer_pack_np."""
+        self._check(self.lib.wq_peer_pack_device(
+            self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in, frames_ptr or None,
+            frame_offsets_ptr or None, n_msgs, n_frame_bytes, flags, out_ptr or None, capacity_bytes,
+            out_peer_bytes_ptr or None, out_elem_bytes_ptr or None, counters_ptr or None))
 
     # ---- interest changes between two ticks (include/wq_router.h; host reference: interest.py) ----
     def csr_diff(self, old_offsets, old_peers, new_offsets, new_peers, with_left: bool = True,
