@@ -896,6 +896,111 @@ int wq_peer_pack_device(wq_router* h,
         uint64_t* d_out_elem_bytes,   /* [n_in], nullable */
         wq_pack_counters* d_counters  /* nullable */);
 
+/* ---- frame builder: a tick's flat messages serialized on the device ----
+ * wq_serialize_messages (wq_codec.h) builds the frames on the host. For entity updates the device
+ * already holds every value that goes into them, so this call writes the same bytes there: the three
+ * arrays it leaves are the d_frames / d_frame_offsets / d_msg_size that wq_peer_pack_device and
+ * wq_peer_budget_bytes_device take, with bytes_need as n_frame_bytes. An extension like the send
+ * buffers: the reference serializes once per message on the host (structures/message.rs:120-134).
+ *
+ * Flat messages
+ *   - A flat message has an instruction, a replication, a sender uuid and a world name, an optional
+ *     position, an optional parameter and an optional flex, and no records and no entities (the two
+ *     vectors are written, empty, as the host writes them). Messages with records or entities stay with
+ *     wq_serialize_messages.
+ * Worlds
+ *   - wq_frames_set_worlds gives the handle the table world id -> name. names / name_offsets are HOST
+ *     arrays: world w is names[name_offsets[w] .. name_offsets[w + 1]), name_offsets has n_worlds + 1
+ *     ascending entries.
+ *   - WQ_E_INVALID, with the old table kept, for offsets that descend (or a null name_offsets) and for
+ *     a name that is not UTF-8 as wq_serialize_message checks it.
+ *   - The table is copied: the caller's arrays are free on return. The call waits for the handle's
+ *     stream, so it is ordered behind earlier builds and before later ones. n_worlds == 0 clears the
+ *     table. It is not a per-tick call.
+ * Source (wq_frames_src: device pointers, any alignment)
+ *   - instruction / replication: u8 per message, or NULL for instruction_all / replication_all.
+ *   - sender_uuid: 16 bytes per message; world: u32 ids into the table. Both required for n_msgs > 0.
+ *   - pos: 3 f64 per message, or NULL: no message has a position.
+ *   - param / param_offsets / n_param_bytes: message i's parameter is param[po[i] .. po[i + 1]), po =
+ *     param_offsets[n_msgs + 1] (u64). NULL / NULL / 0: no message has a parameter. flex likewise.
+ *   - msg_flags: u8 per message, bit 0 position, bit 1 parameter, bit 2 flex: the fields the message
+ *     has. A bit whose array is NULL counts as clear. NULL: every message has every field whose array
+ *     is given.
+ * Byte identity
+ *   - Frame i is byte for byte what wq_serialize_message writes for the message with those fields,
+ *     d_frame_offsets[n_msgs + 1] is what wq_serialize_messages returns in `offsets`, and
+ *     d_frame_size[i] (nullable) is frame i's size. Frame i is d_frames[fo[i] .. fo[i + 1]).
+ *   - Instruction and replication are written as given: 0 is omitted as the default and any other
+ *     value, 255 included, is written, as the host does. Positions are copied as bits, NaN included.
+ *     The uuid's text is lower-case hyphenated.
+ *   - Parameter bytes are NOT checked for UTF-8 on the device (the host serializer refuses such a
+ *     message with WQ_SER_INVALID_UTF8). Byte identity is promised for input the host serializer
+ *     accepts.
+ * Malformed input (never a fault, never fatal; `error` bits)
+ *   - bit 0: a world id >= n_worlds: the world name is empty. With no table set every id is.
+ *   - bit 1: a parameter range that descends, reaches past n_param_bytes or spans 2^32 bytes or more:
+ *     the parameter is present and empty. bit 2: the same for flex.
+ *   - bit 3: a frame above the builder's 2^30 bytes, where the host returns WQ_SER_TOO_LARGE: the
+ *     frame is empty, size 0.
+ *   - Nothing is dereferenced outside the n_msgs-sized arrays, [0, n_msgs] of the offset arrays,
+ *     [0, n_*_bytes) of the payloads and the handle's table, whatever the arrays hold.
+ * Capacity
+ *   - As wq_peer_pack_device: bytes at positions >= capacity_bytes are not written, everything below
+ *     is exact; the offsets, the sizes and the counters are always complete. d_frames == NULL with
+ *     capacity_bytes == 0 is the sizing call, which reads no payload byte. n_complete counts the
+ *     frames that lie wholly below the capacity.
+ * Output guarantees
+ *   - Nothing is written outside d_frames[0 .. bytes_written), d_frame_offsets[0 .. n_msgs],
+ *     d_frame_size[0 .. n_msgs) and the counters. d_frames must be 16-byte aligned (every hipMalloc
+ *     result is), d_frame_offsets 8-byte and d_frame_size 4-byte. Outputs must not alias inputs.
+ *   - Deterministic byte for byte: placement comes from a u64 scan, and the only atomics are ORs into
+ *     the error word.
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. The copy's grid is sized from
+ *     capacity_bytes and walks the output bytes: a wave owns 1 KiB of output and a lane 16 bytes, so no
+ *     lane, wave or block owns a frame or a payload; a tile that lies inside one payload is copied
+ *     with 16-byte loads and stores.
+ *   - Scratch lives in the handle, grow-only: 4 n_msgs + 64 bytes (the sizes and the error word) plus
+ *     the scan's and the world table (each buffer is allocated a quarter above its need). A
+ *     steady-state call does no hipMalloc, and the call may alternate freely with both budget calls
+ *     and wq_peer_pack_device on one handle.
+ * Limits and handle kinds
+ *   - WQ_E_INVALID, with nothing launched, for a null handle, a null src, a null required array with
+ *     n_msgs > 0 (d_frame_offsets is always required), param without param_offsets or the reverse
+ *     (likewise flex), d_frames == NULL with capacity_bytes > 0, a misaligned d_frames and
+ *     n_msgs >= 2^32 - 1.
+ *   - Like wq_peer_pack_device the call needs only a stream, scratch and the table: a multi-GPU handle
+ *     runs it on its own stream with the arrays on devices[0].
+ *   - Building into mapped host memory is not covered here and has not been measured. */
+int wq_frames_set_worlds(wq_router* h, const char* names, const uint32_t* name_offsets, uint32_t n_worlds);
+
+typedef struct wq_frames_src {            /* all device pointers */
+    const uint8_t*  instruction;  uint8_t instruction_all;   /* NULL: every message has instruction_all */
+    const uint8_t*  replication;  uint8_t replication_all;   /* NULL: replication_all */
+    const uint8_t*  sender_uuid;                             /* [16 n], required for n > 0 */
+    const uint32_t* world;                                   /* [n] ids into the handle's table, required */
+    const double*   pos;                                     /* [3 n], NULL: no message has a position */
+    const uint8_t*  param; const uint64_t* param_offsets; uint64_t n_param_bytes;  /* NULL/NULL/0: none */
+    const uint8_t*  flex;  const uint64_t* flex_offsets;  uint64_t n_flex_bytes;
+    const uint8_t*  msg_flags;  /* [n], NULL: every message has every field whose array is given;
+                                   bit 0 position, 1 parameter, 2 flex; a bit whose array is NULL counts as clear */
+} wq_frames_src;            /* 112 bytes */
+
+typedef struct wq_frames_counters {
+    uint64_t n_frames;      /* n_msgs */
+    uint64_t n_complete;    /* frames that lie wholly below capacity_bytes */
+    uint64_t bytes_need;    /* bytes of all frames = d_frame_offsets[n_msgs] */
+    uint64_t bytes_written; /* min(bytes_need, capacity_bytes) */
+    uint32_t overflow;      /* bit 0: bytes_need > capacity_bytes */
+    uint32_t error;         /* bits 0 - 3 above */
+} wq_frames_counters;       /* 40 bytes */
+
+int wq_frames_build_device(wq_router* h, const wq_frames_src* src, size_t n_msgs,
+        uint8_t* d_frames, size_t capacity_bytes,
+        uint64_t* d_frame_offsets /* [n_msgs + 1], required */,
+        uint32_t* d_frame_size    /* [n_msgs], nullable */,
+        wq_frames_counters* d_counters /* nullable */);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

@@ -69,6 +69,29 @@ PACK_ERROR_MSG = 2         # bit 1: a message index was >= n_msgs
 PACK_ERROR_FRAME = 4       # bit 2: a referenced frame's offsets descend, reach past n_frame_bytes or span >= 2^32
 
 
+# struct wq_frames_counters: 40 bytes (wq_frames_build_device)
+FRAMES_COUNTERS_DTYPE = np.dtype([("n_frames", np.uint64), ("n_complete", np.uint64), ("bytes_need", np.uint64),
+                                  ("bytes_written", np.uint64), ("overflow", np.uint32), ("error", np.uint32)])
+FRAME_MAX = 1 << 30          # the builder's limit: the host returns WQ_SER_TOO_LARGE above it
+FRAMES_ERROR_WORLD = 1       # wq_frames_counters.error bit 0: a world id >= n_worlds
+FRAMES_ERROR_PARAM = 2       # bit 1: a parameter range descends, reaches past n_param_bytes or spans >= 2^32
+FRAMES_ERROR_FLEX = 4        # bit 2: the same for flex
+FRAMES_ERROR_TOO_LARGE = 8   # bit 3: a frame above FRAME_MAX, left empty
+FRAMES_HAS_POSITION, FRAMES_HAS_PARAMETER, FRAMES_HAS_FLEX = 1, 2, 4   # wq_frames_src.msg_flags bits
+
+
+class FramesSrc(ctypes.Structure):  # struct wq_frames_src: device pointers
+    _fields_ = [("instruction", ctypes.c_void_p), ("instruction_all", ctypes.c_uint8),
+                ("replication", ctypes.c_void_p), ("replication_all", ctypes.c_uint8),
+                ("sender_uuid", ctypes.c_void_p), ("world", ctypes.c_void_p), ("pos", ctypes.c_void_p),
+                ("param", ctypes.c_void_p), ("param_offsets", ctypes.c_void_p), ("n_param_bytes", ctypes.c_uint64),
+                ("flex", ctypes.c_void_p), ("flex_offsets", ctypes.c_void_p), ("n_flex_bytes", ctypes.c_uint64),
+                ("msg_flags", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(FramesSrc) == 112 and FRAMES_COUNTERS_DTYPE.itemsize == 40
+
+
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]
 

@@ -259,6 +259,11 @@ struct wq_router {
     // send buffers (wq_pack.hip): the rows run on bud_len / bud_sum / bud_pre above; per ordinal the
     // frame's size, where it starts and one u64 scan entry; {unused, error}
     wq::DevBuf pack_size, pack_src, pack_scan, pack_ctrl;
+    // frame builder (wq_frames.hip): per message the frame's size; {unused, error}; the world table
+    // (wq_frames_set_worlds): the names back to back and their n_worlds + 1 offsets
+    wq::DevBuf frm_size, frm_ctrl, frm_world_bytes, frm_world_off;
+    uint32_t frm_n_worlds = 0;
+    uint64_t frm_world_total = 0;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -374,6 +379,13 @@ int launch_peer_pack(wq_router* h, const uint32_t* d_peer_offsets, const uint32_
                      uint32_t flags, uint8_t* d_out, size_t capacity_bytes, uint64_t* d_out_peer_bytes,
                      uint64_t* d_out_elem_bytes, wq_pack_counters* d_counters);
 void pack_release(wq_router* h);
+// wq_frames.hip: the world table's check and upload, the frame builder on device arrays (asynchronous),
+// and the release of both.
+bool frames_worlds_valid(const char* names, const uint32_t* name_offsets, uint32_t n_worlds);
+int frames_set_worlds(wq_router* h, const char* names, const uint32_t* name_offsets, uint32_t n_worlds);
+int launch_frames_build(wq_router* h, const wq_frames_src* src, size_t n_msgs, uint8_t* d_frames, size_t capacity_bytes,
+                        uint64_t* d_frame_offsets, uint32_t* d_frame_size, wq_frames_counters* d_counters);
+void frames_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
 // wq_table_export.hip: frees the export's scratch.

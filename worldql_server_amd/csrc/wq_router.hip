@@ -127,6 +127,7 @@ int wq_router_destroy(wq_router* h) {
     csr_diff_release(h);
     budget_release(h);
     pack_release(h);
+    frames_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -742,6 +743,30 @@ int wq_peer_pack_device(wq_router* h, const uint32_t* d_peer_offsets, const uint
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_peer_pack(h, d_peer_offsets, d_msgs, n_peers, n_in, d_frames, d_frame_offsets, n_msgs, n_frame_bytes,
                             flags, d_out, capacity_bytes, d_out_peer_bytes, d_out_elem_bytes, d_counters);
+}
+
+int wq_frames_set_worlds(wq_router* h, const char* names, const uint32_t* name_offsets, uint32_t n_worlds) {
+    if (!h) return WQ_E_INVALID;
+    if (!frames_worlds_valid(names, name_offsets, n_worlds))
+        return set_error(h, WQ_E_INVALID, "frames_set_worlds: offsets that descend or a name that is not UTF-8");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return frames_set_worlds(h, names, name_offsets, n_worlds);
+}
+
+int wq_frames_build_device(wq_router* h, const wq_frames_src* src, size_t n_msgs, uint8_t* d_frames,
+                           size_t capacity_bytes, uint64_t* d_frame_offsets, uint32_t* d_frame_size,
+                           wq_frames_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!src) return set_error(h, WQ_E_INVALID, "frames_build: src is null");
+    if (!d_frame_offsets || (n_msgs && (!src->sender_uuid || !src->world)))
+        return set_error(h, WQ_E_INVALID, "frames_build: a null required array");
+    if (!src->param != !src->param_offsets || !src->flex != !src->flex_offsets)
+        return set_error(h, WQ_E_INVALID, "frames_build: a payload and its offsets are given together or not at all");
+    if (!d_frames && capacity_bytes) return set_error(h, WQ_E_INVALID, "frames_build: capacity_bytes without d_frames");
+    if ((uintptr_t)d_frames & 15u) return set_error(h, WQ_E_INVALID, "frames_build: d_frames must be 16-byte aligned");
+    if (n_msgs >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "frames_build: n_msgs must be < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_frames_build(h, src, n_msgs, d_frames, capacity_bytes, d_frame_offsets, d_frame_size, d_counters);
 }
 
 // The argument rules both forms of wq_csr_diff share (capacities already clamped to 2^32 - 1).

@@ -339,6 +339,8 @@ class InterestTracker:
         self.diff_cnt = torch.zeros(24, dtype=torch.uint8, device=self.dev)
         self.pack_cnt = torch.zeros(40, dtype=torch.uint8, device=self.dev)
         self.pack_buf = None  # peer_pack's send buffer, grow-only
+        self.frame_cnt = torch.zeros(40, dtype=torch.uint8, device=self.dev)
+        self.frame_buf = None  # build_frames' frame bytes, grow-only
         torch.cuda.synchronize(self.dev)
         self.ticks = 0
 
@@ -456,6 +458,36 @@ class InterestTracker:
         kept = int(oo[n_peers].item()) & 0xFFFFFFFF
         return oo, om[:kept], ob[:n_peers]
 
+    def build_frames(self, src: "abi.FramesSrc"):
+        """The tick's frames built on the device through wq_frames_build_device, for entity updates
+        whose fields are already there (src: abi.FramesSrc of device pointers over the n_rows entities,
+        worlds as ids into the router's set_worlds table): (frames[bytes_need] uint8,
+        frame_offsets[n_rows + 1] int64, frame_size[n_rows] int32 holding the u32 bits). They are what
+        peer_budget_bytes takes as msg_size_ptr and peer_pack as frames_ptr / frame_offsets_ptr /
+        n_frame_bytes (frames.numel()), so a tick goes from positions to packed runs without the host
+        building or uploading a frame. `frames` is a view of the tracker's grow-only buffer, valid until
+        the next call; a buffer that is too small is grown to bytes_need and the call made once more.
+        Error bits (a world id outside the table, a payload range out of bounds, a frame above 2^30
+        bytes) raise."""
+        torch = self.torch
+        n = self.n_rows
+        if self.frame_buf is None:
+            self.frame_buf = torch.empty(1 << 20, dtype=torch.uint8, device=self.dev)
+        fo = torch.empty(n + 1, dtype=torch.int64, device=self.dev)
+        fs = torch.empty(max(n, 1), dtype=torch.int32, device=self.dev)
+        for _ in range(2):
+            torch.cuda.synchronize(self.dev)
+            self.router.build_frames_device(src, n, self.frame_buf.data_ptr(), self.frame_buf.numel(), fo.data_ptr(),
+                                            fs.data_ptr(), self.frame_cnt.data_ptr())
+            c = self._read(self.frame_cnt, abi.FRAMES_COUNTERS_DTYPE)
+            if not c["overflow"]:
+                break
+            need = int(c["bytes_need"])
+            self.frame_buf = torch.empty(need + need // 4, dtype=torch.uint8, device=self.dev)
+        if c["error"]:
+            raise RuntimeError(f"build_frames error bits {int(c['error']):#x}")
+        return self.frame_buf[: int(c["bytes_written"])], fo, fs[:n]
+
     def peer_pack(self, peer_offsets, rows, frames_ptr: int, frame_offsets_ptr: int, n_frame_bytes: int,
                   len_prefix: bool = False):
         """Chains after peer_major or either budget: every observer's frames in one contiguous byte run,
@@ -463,9 +495,9 @@ class InterestTracker:
         elem_bytes[n_in]), the last two int64 tensors; observer p's run is out[peer_bytes[p]:
         peer_bytes[p + 1]] and the record of list element q starts at elem_bytes[q]. frames_ptr /
         frame_offsets_ptr: the tick's frames on the device as wq_serialize_messages leaves them (u8 bytes,
-        u64 offsets[n_rows + 1]), uploaded once per tick. `out` is a view of the tracker's grow-only
-        buffer, valid until the next call; a buffer that is too small is grown to bytes_need and the call
-        made once more."""
+        u64 offsets[n_rows + 1]), uploaded once per tick or built on the device by build_frames. `out` is
+        a view of the tracker's grow-only buffer, valid until the next call; a buffer that is too small
+        is grown to bytes_need and the call made once more."""
         torch = self.torch
         n_peers, n_in = peer_offsets.numel() - 1, rows.numel()
         if self.pack_buf is None:

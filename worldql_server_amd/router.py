@@ -81,6 +81,8 @@ def load_library(build_if_missing: bool = True):
         "wq_peer_budget_bytes_device": ([vp, vp, vp, u32, sz, vp, vp, sz, vp, sz, ctypes.c_uint64, vp, vp, vp, vp, vp],
                                         i32),
         "wq_peer_pack_device": ([vp, vp, vp, u32, sz, vp, vp, sz, sz, u32, vp, sz, vp, vp, vp], i32),
+        "wq_frames_set_worlds": ([vp, vp, vp, u32], i32),
+        "wq_frames_build_device": ([vp, ctypes.POINTER(abi.FramesSrc), sz, vp, sz, vp, vp, vp], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -425,6 +427,29 @@ class Router:
             self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in, frames_ptr or None,
             frame_offsets_ptr or None, n_msgs, n_frame_bytes, flags, out_ptr or None, capacity_bytes,
             out_peer_bytes_ptr or None, out_elem_bytes_ptr or None, counters_ptr or None))
+
+    # ---- frame builder (include/wq_router.h; host definition: frames.py) ----
+    def set_worlds(self, names) -> None:
+        """wq_frames_set_worlds: the handle's table world id -> name (a list of str or bytes; empty
+        clears it) for build_frames_device. The table is copied; the call waits for the handle's stream."""
+        from .frames import world_table
+        raw, off = world_table(names)
+        buf = ctypes.create_string_buffer(raw, max(len(raw), 1))
+        self._check(self.lib.wq_frames_set_worlds(self.h, ctypes.addressof(buf), off.ctypes.data, len(off) - 1))
+
+    def build_frames_device(self, src: "abi.FramesSrc", n_msgs: int, frames_ptr: int | None, capacity_bytes: int,
+                            frame_offsets_ptr: int | None, frame_size_ptr: int | None = None,
+                            counters_ptr: int | None = None) -> None:
+        """wq_frames_build_device: the frames of n_msgs flat messages (src: abi.FramesSrc of device
+        pointers, worlds as ids into set_worlds' table) written to frames_ptr exactly as
+        codec.serialize_messages writes them, their u64 offsets[n_msgs + 1] to frame_offsets_ptr and
+        their u32 sizes to frame_size_ptr (optional): the three arrays peer_budget_bytes_device and
+        peer_pack_device take. Asynchronous on the handle's stream; the counters
+        (abi.FRAMES_COUNTERS_DTYPE) stay where counters_ptr points. frames_ptr None with capacity 0
+        sizes the buffer. Host definition: frames.build_frames_np."""
+        self._check(self.lib.wq_frames_build_device(self.h, ctypes.byref(src), n_msgs, frames_ptr or None,
+                                                    capacity_bytes, frame_offsets_ptr or None, frame_size_ptr or None,
+                                                    counters_ptr or None))
 
     # ---- interest changes between two ticks (include/wq_router.h; host reference: interest.py) ----
     def csr_diff(self, old_offsets, old_peers, new_offsets, new_peers, with_left: bool = True,
