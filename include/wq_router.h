@@ -810,6 +810,106 @@ int wq_peer_budget_bytes_device(wq_router* h,
         uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
         wq_budget_bytes_counters* d_counters);
 
+/* ---- fair share: rotate what the budgets cut so every entity arrives ----
+ * Both budgets keep the nearest messages of a peer's list, every tick the same ones while the crowd
+ * stands still. This call gives a second, small share of the connection's budget to the elements the
+ * budget cut, in turn: per peer one u32 cursor holds a message index, and the cut elements that
+ * follow it in cyclic order of message index are added to the budget's output. The lists ascend by
+ * message index and, for entity workloads, row m of every tick is entity m, so the cursor is an id
+ * that survives lists that change under it. There is no per-pair state. An element that stays in a
+ * peer's list and stays cut is sent at least once every ceil(T / R) ticks, T the row's cut elements
+ * and R its share. The call takes a budget's output and not its rule, so it composes with either
+ * budget or both. An extension like the budgets: the reference has neither.
+ *
+ * Input rows
+ *   - d_peer_offsets[n_peers + 1] / d_msgs[n_in] is the full peer-major CSR, the budget's input.
+ *     d_kept_offsets[n_peers + 1] / d_kept_msgs[n_kept_in] is the kept CSR over the same peers, either
+ *     budget's output on it.
+ *   - Rows, their clamping to their own array, the walk of at most n_in (n_kept_in) elements in total
+ *     and `error` bit 0 are wq_peer_budget_device's, for either CSR.
+ *   - R_p = d_extra[p] (u32 per peer), or r when d_extra is NULL: the count share.
+ *   - d_msg_size[n_msgs] (nullable, then n_msgs is ignored and the share is by count only) gives the
+ *     size of an element as in wq_peer_budget_bytes_device: d_msg_size[m], and 0 without a read when
+ *     m >= n_msgs (`error` bit 1). V_p = d_extra_bytes[p] (u64 per peer), or v when it is NULL: the
+ *     byte share. Without sizes v and d_extra_bytes are ignored.
+ *   - d_cursor[n_peers] is read and written in place. 0xFFFFFFFF starts at the row's beginning, which
+ *     is what a new peer's cursor holds.
+ *   - Nothing is dereferenced outside [0, n_in), [0, n_kept_in), [0, n_peers] of the offsets,
+ *     [0, n_peers) of the per-peer arrays and [0, n_msgs) of d_msg_size, whatever the arrays hold.
+ * Rule, for rows that ascend
+ *   - A value m occurs cf times in full row p and ck times in kept row p. The first min(cf, ck)
+ *     occurrences in the full row are kept, the others are cut. A kept element with no partner
+ *     (ck > cf, or a value the full row does not hold) is ignored and sets `error` bit 2.
+ *   - pos_p is the first index of full row p whose message index is greater than d_cursor[p], the
+ *     row's end when there is none. The cut elements are numbered q = 0, 1, ... from pos_p to the
+ *     row's end, then from the row's start to pos_p.
+ *   - The chosen elements are the longest prefix of that order with q < R_p and, with sizes, a running
+ *     size sum (u64, own size included) <= V_p. When R_p >= 1 the element q = 0 is always chosen: one
+ *     frame larger than V_p cannot block the rotation, and the overshoot is at most that frame.
+ *     R_p == 0 chooses nothing.
+ * Output
+ *   - Row p of d_out_offsets / d_out_msgs holds the kept and the chosen elements of full row p in the
+ *     full row's order (a stable compaction: ascending stays ascending), always a sub-multiset of the
+ *     full row. d_out_offsets[0 .. n_peers] is always written in full, from 0.
+ *   - d_cursor[p] becomes the message index of the chosen element with the largest q, and is left as
+ *     it is when nothing was chosen.
+ *   - d_out_bytes (nullable, needs sizes): entry p is the size sum of output row p, at most
+ *     W_p + V_p + the largest frame after a byte budget W_p: what the pack's buffer is sized from.
+ *   - d_counters is nullable.
+ *   - Nothing is written outside d_out_offsets[0 .. n_peers], d_out_msgs[0 .. n_out), n_out <= n_in,
+ *     d_out_bytes[0 .. n_peers), d_cursor[0 .. n_peers) and the counters. Outputs must not alias
+ *     inputs.
+ *   - Rows that do not ascend give an unspecified but well formed result: offsets ascend from 0,
+ *     d_out_offsets[n_peers] <= n_in, every written index comes from the full row, nothing is touched
+ *     out of bounds, and two calls on the same inputs give the same bytes.
+ *   - The output is deterministic byte for byte: placement comes from prefix sums; the atomics are
+ *     integer adds and ORs into the counters.
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. The grids are sized from n_in and
+ *     n_peers. No lane, wave or block walks a row: an element finds its row, its occurrence index and
+ *     its value's bounds in the kept row by binary search, a peer finds pos_p by binary search, and
+ *     ranks and running bytes are differences of two scans over all elements.
+ *   - d_cursor[p] is read before it is written: read by the pass over the peers that precedes every
+ *     pass over the elements, and written by the call's last kernel.
+ *   - Scratch lives in the handle, grow-only, released with it: the budgets' buffers, shared with
+ *     them, of which this call uses at most 16.5 n_in + 40 + 12 (n_peers + 1) bytes (per element the
+ *     row 4, the size 4 and one u64 scan 8, the last two only with sizes; the flag words), plus
+ *     44 (n_peers + 1) + 4096 bytes of its own (the kept CSR's rows 12, the row's folded scan terms 32,
+     the slots over which the counters' adds are spread), plus
+ *     the scans' (each buffer is allocated a quarter above its need). A steady-state call does no
+ *     hipMalloc, and the call may alternate freely with both budget calls and the pack on one handle.
+ * Limits and handle kinds
+ *   - n_in <= 2^32 - 1, n_kept_in <= 2^32 - 1 and n_peers < 2^32 - 1; n_msgs above 2^32 - 1 counts
+ *     as that.
+ *   - WQ_E_INVALID, with nothing launched, for a null handle, a null required array with a non-zero
+ *     size (d_out_offsets is always required, d_cursor when n_peers > 0), and d_out_bytes without
+ *     d_msg_size.
+ *   - Positions are not needed: a multi-GPU handle runs the call on its own stream with the arrays on
+ *     devices[0], as wq_peer_major_device does. */
+typedef struct wq_rotate_counters {
+    uint64_t n_in;          /* elements inside the clamped full rows */
+    uint64_t n_kept_in;     /* elements of them matched by a kept element */
+    uint64_t n_chosen;      /* cut elements chosen */
+    uint64_t n_out;         /* elements written = out_offsets[n_peers] = n_kept_in + n_chosen */
+    uint64_t bytes_chosen;  /* sum of the sizes of the chosen elements (0 without sizes) */
+    uint64_t bytes_out;     /* sum of the sizes of the written ones (0 without sizes) */
+    uint32_t rows_rotated;  /* rows with at least one chosen element */
+    uint32_t rows_behind;   /* rows that still have cut elements not chosen */
+    uint32_t error;         /* bit 0: a row of either CSR descended or reached past its array;
+                               bit 1: with sizes, a full element's message index was >= n_msgs;
+                               bit 2: a kept element had no partner in its full row */
+    uint32_t pad_;
+} wq_rotate_counters;       /* 64 bytes */
+int wq_peer_rotate_device(wq_router* h,
+        const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
+        const uint32_t* d_kept_offsets, const uint32_t* d_kept_msgs, size_t n_kept_in,
+        const uint32_t* d_msg_size, size_t n_msgs,          /* nullable pair: count share only */
+        uint32_t r, const uint32_t* d_extra,
+        uint64_t v, const uint64_t* d_extra_bytes,
+        uint32_t* d_cursor,                                   /* [n_peers], in place, required */
+        uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
+        wq_rotate_counters* d_counters);
+
 /* ---- send buffers: every peer's frames packed into one contiguous byte run ----
  * The budgets leave, per peer, a list of message indices, and wq_serialize_messages leaves the tick's
  * frames in one array (frame i is out[offsets[i] .. offsets[i + 1])). This call does the fan-out on

@@ -60,6 +60,16 @@ BUDGET_ERROR_MSG = 2       # bit 1: a message index was >= n_msgs
 BUDGET_BYTES_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_kept", np.uint64), ("bytes_in", np.uint64),
                                         ("bytes_kept", np.uint64), ("rows_cut", np.uint32), ("error", np.uint32)])
 
+# struct wq_rotate_counters: 64 bytes (wq_peer_rotate_device)
+ROTATE_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_kept_in", np.uint64), ("n_chosen", np.uint64),
+                                  ("n_out", np.uint64), ("bytes_chosen", np.uint64), ("bytes_out", np.uint64),
+                                  ("rows_rotated", np.uint32), ("rows_behind", np.uint32), ("error", np.uint32),
+                                  ("pad_", np.uint32)])
+ROTATE_ERROR_ROWS = 1      # wq_rotate_counters.error bit 0: a row of either CSR descended or reached past its array
+ROTATE_ERROR_MSG = 2       # bit 1: with sizes, a message index was >= n_msgs
+ROTATE_ERROR_KEPT = 4      # bit 2: a kept element had no partner in its full row
+ROTATE_CURSOR_START = 0xFFFFFFFF   # a new peer's cursor: the rotation starts at the row's beginning
+
 # struct wq_pack_counters: 40 bytes (wq_peer_pack_device)
 PACK_COUNTERS_DTYPE = np.dtype([("n_in", np.uint64), ("n_complete", np.uint64), ("bytes_need", np.uint64),
                                 ("bytes_written", np.uint64), ("overflow", np.uint32), ("error", np.uint32)])

@@ -256,6 +256,10 @@ struct wq_router {
     // calls under a clean-byte count of its own, so the two calls alternate on one handle
     wq::DevBuf byt_size, byt_scan, byt_sel, byt_hist;
     size_t byt_hist_clean = 0;
+    // fair share (wq_rotate.hip): it runs on the buffers above (the full CSR's rows, the per-ordinal
+    // row and size, the u64 scan, the flag words, ctrl) and adds the kept CSR's rows and, per peer, the
+    // folded scan terms of its row (RotRow), and the slots the counters' adds are spread over
+    wq::DevBuf rot_len, rot_sum, rot_pre, rot_rows, rot_part;
     // send buffers (wq_pack.hip): the rows run on bud_len / bud_sum / bud_pre above; per ordinal the
     // frame's size, where it starts and one u64 scan entry; {unused, error}
     wq::DevBuf pack_size, pack_src, pack_scan, pack_ctrl;
@@ -373,6 +377,13 @@ int launch_peer_budget_bytes(wq_router* h, const uint32_t* d_peer_offsets, const
                              uint32_t* d_out_offsets, uint32_t* d_out_msgs, uint64_t* d_out_bytes,
                              wq_budget_bytes_counters* d_counters);
 void budget_release(wq_router* h);
+// wq_rotate.hip: the fair share on device arrays (asynchronous), and its scratch's release.
+int launch_peer_rotate(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
+                       size_t n_in, const uint32_t* d_kept_offsets, const uint32_t* d_kept_msgs, size_t n_kept_in,
+                       const uint32_t* d_msg_size, size_t n_msgs, uint32_t r, const uint32_t* d_extra, uint64_t v,
+                       const uint64_t* d_extra_bytes, uint32_t* d_cursor, uint32_t* d_out_offsets,
+                       uint32_t* d_out_msgs, uint64_t* d_out_bytes, wq_rotate_counters* d_counters);
+void rotate_release(wq_router* h);
 // wq_pack.hip: the send buffers on device arrays (asynchronous), and its scratch's release.
 int launch_peer_pack(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
                      const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_msgs, size_t n_frame_bytes,

@@ -126,6 +126,7 @@ int wq_router_destroy(wq_router* h) {
     follow_release(h);
     csr_diff_release(h);
     budget_release(h);
+    rotate_release(h);
     pack_release(h);
     frames_release(h);
     records_release(h);
@@ -725,6 +726,25 @@ int wq_peer_budget_bytes_device(wq_router* h, const uint32_t* d_peer_offsets, co
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_peer_budget_bytes(h, d_peer_offsets, d_msgs, n_peers, n_in, d_msg_pos, d_msg_size, n_msgs, d_peer_pos,
                                     n_peer_pos, w, d_budget_bytes, d_out_offsets, d_out_msgs, d_out_bytes, d_counters);
+}
+
+int wq_peer_rotate_device(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
+                          size_t n_in, const uint32_t* d_kept_offsets, const uint32_t* d_kept_msgs, size_t n_kept_in,
+                          const uint32_t* d_msg_size, size_t n_msgs, uint32_t r, const uint32_t* d_extra, uint64_t v,
+                          const uint64_t* d_extra_bytes, uint32_t* d_cursor, uint32_t* d_out_offsets,
+                          uint32_t* d_out_msgs, uint64_t* d_out_bytes, wq_rotate_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!d_out_offsets || (n_peers && (!d_peer_offsets || !d_kept_offsets || !d_cursor)) ||
+        (n_in && (!d_msgs || !d_out_msgs)) || (n_kept_in && !d_kept_msgs))
+        return set_error(h, WQ_E_INVALID, "peer_rotate: a null array with a non-zero size");
+    if (d_out_bytes && !d_msg_size) return set_error(h, WQ_E_INVALID, "peer_rotate: d_out_bytes needs d_msg_size");
+    if (n_in > 0xFFFFFFFFull || n_kept_in > 0xFFFFFFFFull || n_peers == 0xFFFFFFFFu)
+        return set_error(h, WQ_E_INVALID,
+                         "peer_rotate: n_in and n_kept_in must be <= 2^32 - 1 and n_peers < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_peer_rotate(h, d_peer_offsets, d_msgs, n_peers, n_in, d_kept_offsets, d_kept_msgs, n_kept_in,
+                              d_msg_size, n_msgs, r, d_extra, v, d_extra_bytes, d_cursor, d_out_offsets, d_out_msgs,
+                              d_out_bytes, d_counters);
 }
 
 int wq_peer_pack_device(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,

@@ -13,6 +13,8 @@ csrc/wq_budget.hip): of every peer's list the min(budget, len) messages nearest 
 peer's list the nearest messages whose sizes sum to at most the peer's bytes.
 `peer_pack_np` is the definition of the send buffers (wq_peer_pack_device, csrc/wq_pack.hip): every
 peer's frames in one contiguous byte run, in list order.
+`peer_rotate_np` is the definition of the fair share (wq_peer_rotate_device, csrc/wq_rotate.hip): the
+budget's output plus, per peer, the cut elements that follow the peer's cursor in cyclic order.
 """
 from __future__ import annotations
 
@@ -257,6 +259,117 @@ def peer_budget_bytes_np(peer_offsets, msgs, msg_pos, msg_size, peer_pos, w=None
                                               error=error)
 
 
+def _walk_rows(offsets, n):
+    """The budgets' rows of a CSR over an array of n elements: per row (start, length) after the clamp
+    to [0, n) and the walk of at most n elements in total; (rows, walked, error bit 0)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).astype(np.int64)
+    rows, walked, error = [], 0, 0
+    for p in range(max(len(off) - 1, 0)):
+        a, b = min(off[p], n), min(off[p + 1], n)
+        b = max(a, b)
+        if off[p] > off[p + 1] or off[p + 1] > n:
+            error |= 1
+        ln = min(b - a, n - walked)
+        if ln != b - a:
+            error |= 1
+        walked += ln
+        rows.append((int(a), int(ln)))
+    return rows, walked, error
+
+
+def peer_rotate_np(peer_offsets, msgs, kept_offsets, kept_msgs, cursor, r=None, extra=None, msg_size=None,
+                   v=None, extra_bytes=None):
+    """The fair share, the definition of what wq_peer_rotate_device writes. The full peer-major CSR
+    (peer_offsets[n_peers + 1], msgs[n_in]) and a kept CSR over the same peers (either budget's output
+    on it); cursor[n_peers] u32, a message index per peer, read and written IN PLACE. Returns
+    (out_offsets[n_peers + 1], out_msgs[n_out], out_bytes[n_peers] u64 or None without sizes, counters)
+    with counters a dict of n_in, n_kept_in, n_chosen, n_out, bytes_chosen, bytes_out, rows_rotated,
+    rows_behind, error.
+
+    Rows of both CSRs are peer_budget_np's (error bit 0). For rows that ascend: a value that occurs cf
+    times in full row p and ck times in kept row p has its first min(cf, ck) occurrences kept, the others
+    cut; a kept element without a partner is ignored (error bit 2). The cut elements are numbered
+    q = 0, 1, ... from the first index whose message index is greater than cursor[p] to the row's end,
+    then from the row's start. Chosen is the longest prefix of that order with q < R_p (extra[p], or r)
+    and, with msg_size, a running size sum <= V_p (extra_bytes[p], or v); q = 0 is always chosen when
+    R_p >= 1. The size of message m is msg_size[m], and 0 when m >= len(msg_size) (error bit 1). Output
+    row p: the kept and the chosen elements in the full row's order; cursor[p]: the message index of the
+    chosen element with the largest q, unchanged when there is none. The sums are Python ints. Row by
+    row, for clarity."""
+    import bisect
+    from collections import Counter
+    msgs = np.ascontiguousarray(msgs, dtype=np.uint32)
+    kept_msgs = np.ascontiguousarray(kept_msgs, dtype=np.uint32)
+    n_in, n_kin = len(msgs), len(kept_msgs)
+    rows, walked, error = _walk_rows(peer_offsets, n_in)
+    krows, _, kerror = _walk_rows(kept_offsets, n_kin)
+    error |= kerror
+    n_peers = len(rows)
+    if len(krows) != n_peers or len(cursor) < n_peers:
+        raise ValueError("the kept CSR and the cursors cover the full CSR's peers")
+    if cursor.dtype != np.uint32:
+        raise ValueError("cursor is a u32 array, written in place")
+    if extra is None and r is None:
+        raise ValueError("give r or a per-peer share")
+    sizes_on = msg_size is not None
+    if sizes_on:
+        msg_size = np.ascontiguousarray(msg_size, dtype=np.uint32)
+        if extra_bytes is None and v is None:
+            raise ValueError("with msg_size give v or a per-peer byte share")
+    n_msgs = len(msg_size) if sizes_on else 0
+    out_off = np.zeros(n_peers + 1, dtype=np.uint32)
+    out_bytes = np.zeros(n_peers, dtype=np.uint64) if sizes_on else None
+    out, matched, n_chosen, bytes_chosen, bytes_out, rows_rotated, rows_behind = [], 0, 0, 0, 0, 0, 0
+    for p in range(n_peers):
+        (a, n), (ka, kn) = rows[p], krows[p]
+        row = msgs[a:a + n].tolist()
+        have = Counter(kept_msgs[ka:ka + kn].tolist())
+        size = [0] * n
+        if sizes_on:
+            if any(m >= n_msgs for m in row):
+                error |= 2
+            size = [int(msg_size[m]) if m < n_msgs else 0 for m in row]
+        seen, is_cut = Counter(), []
+        for m in row:
+            is_cut.append(seen[m] >= have[m])
+            seen[m] += 1
+        n_match = n - sum(is_cut)
+        matched += n_match
+        if n_match != kn:
+            error |= 4
+        pos = bisect.bisect_right(row, int(cursor[p]))
+        order = [i for i in range(pos, n) if is_cut[i]] + [i for i in range(pos) if is_cut[i]]
+        R = int(extra[p]) if extra is not None else int(r)
+        V = (int(extra_bytes[p]) if extra_bytes is not None else int(v)) if sizes_on else 0
+        chosen, running = [], 0
+        for q, i in enumerate(order):
+            if q >= R:
+                break
+            running += size[i]
+            if sizes_on and q > 0 and running > V:
+                break
+            chosen.append(i)
+        if chosen:
+            cursor[p] = row[chosen[-1]]
+            rows_rotated += 1
+        if len(chosen) < len(order):
+            rows_behind += 1
+        n_chosen += len(chosen)
+        bytes_chosen += sum(size[i] for i in chosen)
+        picked = set(chosen)
+        keep = [i for i in range(n) if not is_cut[i] or i in picked]
+        out.append(np.array([row[i] for i in keep], dtype=np.uint32))
+        out_off[p + 1] = out_off[p] + len(keep)
+        row_bytes = sum(size[i] for i in keep)
+        bytes_out += row_bytes
+        if sizes_on:
+            out_bytes[p] = row_bytes
+    out_msgs = np.concatenate(out).astype(np.uint32) if out else np.zeros(0, np.uint32)
+    return out_off, out_msgs, out_bytes, dict(
+        n_in=walked, n_kept_in=matched, n_chosen=n_chosen, n_out=int(out_off[-1]), bytes_chosen=bytes_chosen,
+        bytes_out=bytes_out, rows_rotated=rows_rotated, rows_behind=rows_behind, error=error)
+
+
 def peer_pack_np(peer_offsets, msgs, frames, frame_offsets, len_prefix=False, capacity=None):
     """Send buffers, the definition of what wq_peer_pack_device writes: for every row of the peer-major
     CSR (peer_offsets[n_peers + 1], msgs[n_in]) the records of its elements, in list order, in one byte
@@ -341,6 +454,7 @@ class InterestTracker:
         self.pack_buf = None  # peer_pack's send buffer, grow-only
         self.frame_cnt = torch.zeros(40, dtype=torch.uint8, device=self.dev)
         self.frame_buf = None  # build_frames' frame bytes, grow-only
+        self.cursor = None     # peer_rotate's u32 cursor per observer (a message index), on the device
         torch.cuda.synchronize(self.dev)
         self.ticks = 0
 
@@ -457,6 +571,45 @@ class InterestTracker:
         torch.cuda.synchronize(self.dev)
         kept = int(oo[n_peers].item()) & 0xFFFFFFFF
         return oo, om[:kept], ob[:n_peers]
+
+    def peer_rotate(self, peer_offsets, rows, kept_offsets, kept_rows, r: int | None = None,
+                    extra_ptr: int | None = None, msg_size_ptr: int | None = None, v: int | None = None,
+                    extra_bytes_ptr: int | None = None):
+        """Chains after peer_budget / peer_budget_bytes: the budget's output (kept_offsets, kept_rows) of
+        the lists (peer_offsets, rows) plus, per observer, the cut entities that follow its cursor in
+        cyclic order of entity index, at most r of them (extra_ptr: u32 per observer) and, with
+        msg_size_ptr, at most v bytes (extra_bytes_ptr: u64 per observer), through
+        wq_peer_rotate_device: (out_offsets[n_peers + 1], out_rows[n_out], out_bytes[n_peers] or None
+        without sizes). The tracker owns the cursors (self.cursor, one u32 per observer on the device,
+        0xFFFFFFFF for an observer not seen before) and they move with every call, so an entity that
+        stays in an observer's list and stays cut arrives within ceil(cut / r) ticks. The call is
+        enqueued and nothing is read back: out_rows is the whole buffer (n_in elements), of which
+        out_offsets[n_peers] are valid, and feeds peer_pack with n_in = rows.numel() unchanged."""
+        torch = self.torch
+        if r is None and extra_ptr is None:
+            raise ValueError("give r or extra_ptr")
+        if msg_size_ptr is not None and v is None and extra_bytes_ptr is None:
+            raise ValueError("with msg_size_ptr give v or extra_bytes_ptr")
+        n_peers, n_in, n_kin = peer_offsets.numel() - 1, rows.numel(), kept_rows.numel()
+        if kept_offsets.numel() != n_peers + 1:
+            raise ValueError("the kept lists cover the same observers")
+        have = 0 if self.cursor is None else self.cursor.numel()
+        if have < n_peers:
+            grown = torch.full((n_peers,), -1, dtype=torch.int32, device=self.dev)
+            if have:
+                grown[:have] = self.cursor
+            self.cursor = grown
+        oo = torch.empty(n_peers + 1, dtype=torch.int32, device=self.dev)
+        om = torch.empty(max(n_in, 1), dtype=torch.int32, device=self.dev)
+        ob = torch.empty(max(n_peers, 1), dtype=torch.int64, device=self.dev) if msg_size_ptr is not None else None
+        torch.cuda.synchronize(self.dev)   # torch's stream filled the cursors; the call runs on the handle's
+        self.router.peer_rotate_device(peer_offsets.data_ptr(), rows.data_ptr() if n_in else None, n_peers, n_in,
+                                       kept_offsets.data_ptr(), kept_rows.data_ptr() if n_kin else None, n_kin,
+                                       msg_size_ptr, self.n_rows if msg_size_ptr is not None else 0, r or 0, extra_ptr,
+                                       v or 0, extra_bytes_ptr, self.cursor.data_ptr() if n_peers else None,
+                                       oo.data_ptr(), om.data_ptr() if n_in else None,
+                                       ob.data_ptr() if ob is not None else None, None)
+        return oo, om[:n_in], (ob[:n_peers] if ob is not None else None)
 
     def build_frames(self, src: "abi.FramesSrc"):
         """The tick's frames built on the device through wq_frames_build_device, for entity updates

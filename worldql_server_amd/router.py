@@ -80,6 +80,8 @@ def load_library(build_if_missing: bool = True):
         "wq_peer_budget_device": ([vp, vp, vp, u32, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp], i32),
         "wq_peer_budget_bytes_device": ([vp, vp, vp, u32, sz, vp, vp, sz, vp, sz, ctypes.c_uint64, vp, vp, vp, vp, vp],
                                         i32),
+        "wq_peer_rotate_device": ([vp, vp, vp, u32, sz, vp, vp, sz, vp, sz, u32, vp, ctypes.c_uint64, vp, vp, vp, vp, vp,
+                                   vp], i32),
         "wq_peer_pack_device": ([vp, vp, vp, u32, sz, vp, vp, sz, sz, u32, vp, sz, vp, vp, vp], i32),
         "wq_frames_set_worlds": ([vp, vp, vp, u32], i32),
         "wq_frames_build_device": ([vp, ctypes.POINTER(abi.FramesSrc), sz, vp, sz, vp, vp, vp], i32),
@@ -411,6 +413,26 @@ class Router:
             self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in, msg_pos_ptr or None, msg_size_ptr or None,
             n_msgs, peer_pos_ptr or None, n_peer_pos, w, budget_bytes_ptr or None, out_offsets_ptr or None,
             out_msgs_ptr or None, out_bytes_ptr or None, counters_ptr or None))
+
+    def peer_rotate_device(self, peer_offsets_ptr: int | None, msgs_ptr: int | None, n_peers: int, n_in: int,
+                           kept_offsets_ptr: int | None, kept_msgs_ptr: int | None, n_kept_in: int,
+                           msg_size_ptr: int | None, n_msgs: int, r: int, extra_ptr: int | None, v: int,
+                           extra_bytes_ptr: int | None, cursor_ptr: int | None, out_offsets_ptr: int | None,
+                           out_msgs_ptr: int | None, out_bytes_ptr: int | None = None,
+                           counters_ptr: int | None = None) -> None:
+        """wq_peer_rotate_device: the fair share. Of every row of the full peer-major CSR the elements
+        the kept CSR (either budget's output on it) holds, plus the cut elements that follow the peer's
+        cursor (cursor_ptr: u32 per peer, a message index, updated in place) in cyclic order of message
+        index: at most extra_ptr[p] of them (u32 per peer, else r for everyone) and, with msg_size_ptr
+        (u32 per message), at most extra_bytes_ptr[p] bytes (u64 per peer, else v), the first always;
+        asynchronous on the handle's stream. out_bytes_ptr (u64 per peer, optional, needs msg_size_ptr)
+        receives every output row's bytes; the counters (abi.ROTATE_COUNTERS_DTYPE) stay where
+        counters_ptr points. Host definition: interest.peer_rotate_np."""
+        self._check(self.lib.wq_peer_rotate_device(
+            self.h, peer_offsets_ptr or None, msgs_ptr or None, n_peers, n_in, kept_offsets_ptr or None,
+            kept_msgs_ptr or None, n_kept_in, msg_size_ptr or None, n_msgs, r, extra_ptr or None, v,
+            extra_bytes_ptr or None, cursor_ptr or None, out_offsets_ptr or None, out_msgs_ptr or None,
+            out_bytes_ptr or None, counters_ptr or None))
 
     def peer_pack_device(self, peer_offsets_ptr: int | None, msgs_ptr: int | None, n_peers: int, n_in: int,
                          frames_ptr: int | None, frame_offsets_ptr: int | None, n_msgs: int, n_frame_bytes: int,
