@@ -52,6 +52,8 @@ extern "C" {
 #define WQ_REPL_ONLY_SELF 2
 
 #define WQ_WORLD_INVALID 0xFFFFFFFFu
+#define WQ_WORLD_GLOBAL 0xFFFFFFFEu /* reserved: the "@global" world as wq_frames_decode_device reports it;
+                                       never an id of the subscription table or of wq_frames_set_worlds */
 
 typedef struct wq_router wq_router;
 
@@ -1101,6 +1103,93 @@ int wq_frames_build_device(wq_router* h, const wq_frames_src* src, size_t n_msgs
         uint32_t* d_frame_size    /* [n_msgs], nullable */,
         wq_frames_counters* d_counters /* nullable */);
 
+/* ---- ingest: a tick's received frames decoded on the device ----
+ * wq_decode_messages (wq_codec.h) verifies and decodes a tick's frames on the host's cores; the host then
+ * sanitizes and interns one world name and looks up one sender uuid per message and uploads four arrays
+ * before wq_route_tick_device or wq_follow_peers_device can start. Here the raw frames are uploaded once
+ * and verified, decoded and resolved where they land: pos / world / sender / repl are the arrays those
+ * calls take. An extension like the frame builder: the reference decodes one message at a time on the
+ * host (structures/message.rs:136-142). The contract is wq_decode_messages'.
+ *
+ * Decode
+ *   - Frame i is d_frames[fo[i] .. fo[i + 1]), fo = d_frame_offsets[n_frames + 1], at any alignment.
+ *   - Every check of wq_decode_messages, in its order: the FlatBuffers 2.0.0 verifier over Message,
+ *     Record and Entity (aligned in-bounds offsets, even vtables, UTF-8 strings with a NUL behind them,
+ *     the 2^31 apparent-size, 1,000,000-table and depth limits), then the decode rules (required fields,
+ *     records before entities, the uuid's three text forms, instruction codes above 12 become 255,
+ *     replication codes above 2 become 0). out->msg[i] is byte for byte what wq_decode_messages writes
+ *     for that frame, failed frames included (the struct is zeroed first and has no padding).
+ * SoA outputs (wq_ingest_out: device pointers, each nullable; msg and pos 8-byte aligned, the u32 arrays 4)
+ *   - pos, repl, instruction, sender_uuid repeat the struct's fields; flex_range is the one it lacks: where
+ *     Message.flex lies inside the frame and its length, 0, 0 when absent.
+ *   - flags: bit 0 status OK, 1 position, 2 parameter, 3 flex, 4 the world is "@global", 5 the world was
+ *     found in the table, 6 the sender was found in the table.
+ *   - A frame that is not OK has zeros in all of them, flags 0, world WQ_WORLD_INVALID and sender
+ *     0xFFFFFFFF, so it routes to nobody.
+ * Worlds
+ *   - A decoded world name of exactly "@global" gives WQ_WORLD_GLOBAL (flag bit 4, bit 5 clear).
+ *   - Every other name goes through wq_sanitize_world_name's rules on the device, and the result is looked
+ *     up among the names of wq_frames_set_worlds: the lowest id with that name wins. A sanitize error, a
+ *     name the table does not hold and a handle without a table give WQ_WORLD_INVALID with bit 5 clear,
+ *     and count in n_world_unresolved.
+ * Senders
+ *   - wq_ingest_set_peers copies a uuid -> id table (HOST arrays: 16 bytes per uuid; ids NULL: id = index)
+ *     into the handle. Not a per-tick call: it sorts on the host and waits for the handle's stream.
+ *     n == 0 clears the table. WQ_E_INVALID, with the old table kept, for a uuid that occurs twice or a
+ *     null uuids with n > 0.
+ *   - A sender the table lacks gives 0xFFFFFFFF (bit 6 clear, counted in n_sender_unknown); its uuid is in
+ *     sender_uuid, so the host handles the tick's few joins and not every message.
+ * Hostile input (never a fault, never fatal)
+ *   - error bit 0: an offset is suspect when it lies past n_frame_bytes or stands in a descending pair
+ *     (either side may be the wrong one). A frame with a suspect offset — its own pair descends or
+ *     reaches past the end, or a neighbour's does at the offset they share — cannot be told from its
+ *     neighbours and is WQ_DEC_INVALID_FLATBUFFER; every other frame is decoded as usual.
+ *     (wq_decode_messages returns -1 for the whole call when offsets descend: the one difference.)
+ *   - error bit 1: a frame of 2^32 bytes or more is WQ_DEC_INVALID_FLATBUFFER. Parity is promised below.
+ *   - No byte is read outside d_frames[0 .. n_frame_bytes) and d_frame_offsets[0 .. n_frames], whatever
+ *     the frames say; every loop over frame content is bounded by the frame's size or the verifier's
+ *     limits; nothing spins.
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. Three launches: the walk (one lane per
+ *     frame; strings of up to 256 bytes are validated there), the long strings (longer strings go through
+ *     a fixed-capacity work list and are validated 16 bytes per lane; a lane that finds the list full
+ *     validates its string itself, with the same result), the finish (frames a long string overturned,
+ *     and the counters: per-block sums added with integer atomics). Deterministic byte for byte.
+ *   - Scratch lives in the handle, grow-only: 4 n_frames bytes, the work list (16 bytes an entry, 65,536
+ *     entries) and 128 bytes. A steady-state call does no hipMalloc, and the call alternates freely with
+ *     the route, budget, builder and pack calls on one handle.
+ * Limits and handle kinds
+ *   - WQ_E_INVALID, with nothing launched, for a null handle or out, a null d_frame_offsets with
+ *     n_frames > 0, a null d_frames with n_frame_bytes > 0 and n_frames >= 2^32 - 1.
+ *   - A multi-GPU handle runs the call on its own stream with the arrays on devices[0], as the builder.
+ *   - Compacting parameter and flex payloads for wq_frames_build_device, and mapped host memory, are not
+ *     covered here. */
+int wq_ingest_set_peers(wq_router* h, const uint8_t* uuids /* host, [16 n] */,
+                        const uint32_t* ids /* host, [n], NULL: id = index */, uint32_t n);
+
+typedef struct wq_ingest_out {       /* device pointers, each nullable */
+    struct wq_decoded_msg* msg;      /* [n]   byte for byte what wq_decode_messages writes (wq_codec.h) */
+    double*   pos;                   /* [3 n] */
+    uint32_t* world;                 /* [n]   world id, WQ_WORLD_GLOBAL, or WQ_WORLD_INVALID */
+    uint32_t* sender;                /* [n]   peer id, or 0xFFFFFFFF */
+    uint8_t*  repl;                  /* [n] */
+    uint8_t*  instruction;           /* [n] */
+    uint8_t*  sender_uuid;           /* [16 n] */
+    uint32_t* flex_range;            /* [2 n] off, len inside the frame; 0, 0 when absent */
+    uint8_t*  flags;                 /* [n] bits 0 - 6 above */
+} wq_ingest_out;            /* 72 bytes */
+
+typedef struct wq_ingest_counters {
+    uint64_t n_frames, n_ok, n_invalid, n_missing, n_bad_uuid;  /* frames per status */
+    uint64_t n_world_unresolved, n_sender_unknown;              /* among the OK frames */
+    uint32_t error;         /* bits 0 and 1 above */
+    uint32_t pad_;
+} wq_ingest_counters;       /* 64 bytes */
+
+int wq_frames_decode_device(wq_router* h, const uint8_t* d_frames, const uint64_t* d_frame_offsets,
+                            size_t n_frames, size_t n_frame_bytes,
+                            const wq_ingest_out* out, wq_ingest_counters* d_counters /* nullable */);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its
@@ -1271,6 +1360,9 @@ int wq_debug_update_counts(wq_router* h, uint64_t* incremental, uint64_t* rebuil
 /* ---- tuning hook: select a compiled route-kernel shape (messages per thread, expansion chunk);
  * 0 is the default. Results are identical for every shape. */
 int wq_debug_set_route_config(wq_router* h, int cfg);
+/* ---- test hook: the capacity of wq_frames_decode_device's long-string work list in entries (0: every
+ * lane validates its long strings itself; negative: the default). Results are identical for every value. */
+int wq_debug_set_ingest_list(wq_router* h, int64_t entries);
 /* ---- tuning hook: the heavy-fan-out tick (count / scan / emit) in `chunks` pipelined chunks — the
  * chunks' counts on a side stream, each chunk's scan and emit on the launch stream as soon as its
  * count is done (0 = the default; 1 = one chunk). Applies to ticks of >= 2 chunks of at most 8,192

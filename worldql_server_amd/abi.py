@@ -26,6 +26,7 @@ REPL_INCLUDING_SELF = 1
 REPL_ONLY_SELF = 2
 
 WORLD_INVALID = 0xFFFFFFFF
+WORLD_GLOBAL = 0xFFFFFFFE          # WQ_WORLD_GLOBAL: "@global" as wq_frames_decode_device reports it
 
 MAX_PAIRS = 0xFFFFFFFF             # pairs per tick: the CSR offsets are u32 (error bit 2, WQ_E_CAPACITY beyond)
 ROUTE_ERROR_PAIR_LIMIT = 2         # wq_route_counters.error bit 2
@@ -100,6 +101,29 @@ class FramesSrc(ctypes.Structure):  # struct wq_frames_src: device pointers
 
 
 assert ctypes.sizeof(FramesSrc) == 112 and FRAMES_COUNTERS_DTYPE.itemsize == 40
+
+
+# struct wq_ingest_counters: 64 bytes (wq_frames_decode_device)
+INGEST_COUNTERS_DTYPE = np.dtype([("n_frames", np.uint64), ("n_ok", np.uint64), ("n_invalid", np.uint64),
+                                  ("n_missing", np.uint64), ("n_bad_uuid", np.uint64),
+                                  ("n_world_unresolved", np.uint64), ("n_sender_unknown", np.uint64),
+                                  ("error", np.uint32), ("pad_", np.uint32)])
+INGEST_ERROR_OFFSETS = 1     # wq_ingest_counters.error bit 0: a frame's offsets descend or reach past n_frame_bytes
+INGEST_ERROR_HUGE = 2        # bit 1: a frame of 2^32 bytes or more
+INGEST_NO_PEER = 0xFFFFFFFF  # wq_ingest_out.sender of a uuid the table lacks (processing.NO_PEER)
+# wq_ingest_out.flags bits
+INGEST_OK, INGEST_HAS_POSITION, INGEST_HAS_PARAMETER, INGEST_HAS_FLEX = 1, 2, 4, 8
+INGEST_WORLD_GLOBAL, INGEST_WORLD_KNOWN, INGEST_SENDER_KNOWN = 16, 32, 64
+INGEST_LANE_STRING = 256     # strings up to this many bytes are validated by the walking lane
+INGEST_CHUNK = 16            # bytes one lane validates of a longer string
+
+
+class IngestOut(ctypes.Structure):  # struct wq_ingest_out: device pointers, each nullable
+    _fields_ = [(k, ctypes.c_void_p) for k in ("msg", "pos", "world", "sender", "repl", "instruction", "sender_uuid",
+                                               "flex_range", "flags")]
+
+
+assert ctypes.sizeof(IngestOut) == 72 and INGEST_COUNTERS_DTYPE.itemsize == 64
 
 
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array

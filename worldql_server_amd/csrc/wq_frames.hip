@@ -20,6 +20,7 @@
 //
 // No lane, wave or block owns a frame or a payload: a 1 MiB flex is a thousand tiles. Placement comes
 // from the scan alone; the only atomics are ORs into the error word.
+#include "decode_ops.hpp"
 #include "frame_ops.hpp"
 #include "table_prims.hpp"
 
@@ -29,6 +30,7 @@ namespace {
 
 static_assert(sizeof(wq_frames_counters) == 40, "wq_frames_counters is 40 bytes");
 static_assert(sizeof(wq_frames_src) == 112, "abi.FramesSrc mirrors this layout");
+static_assert(kDecWorldSlack == kFrWorldSlack, "the ingest decoder reads the same table");
 
 struct FrameTerm {
     const uint32_t* size;
@@ -165,6 +167,8 @@ int frames_set_worlds(wq_router* h, const char* names, const uint32_t* name_offs
         WQ_HIP(h, hipMemcpyAsync(h->frm_world_bytes.as<uint8_t>() + kFrWorldSlack, names + first, total,
                                  hipMemcpyHostToDevice, h->stream));
     WQ_HIP(h, hipStreamSynchronize(h->stream));
+    // the order wq_frames_decode_device looks a name up in, beside the table
+    if (int rc = ingest_set_world_index(h, reinterpret_cast<const uint8_t*>(names) + first, off.data(), n_worlds)) return rc;
     h->frm_n_worlds = n_worlds;
     h->frm_world_total = total;
     return WQ_OK;

@@ -268,6 +268,12 @@ struct wq_router {
     wq::DevBuf frm_size, frm_ctrl, frm_world_bytes, frm_world_off;
     uint32_t frm_n_worlds = 0;
     uint64_t frm_world_total = 0;
+    // ingest decoder (wq_decode.hip): per frame the word between the passes; the long-string work list;
+    // the counters and behind them the list's count; the world table's lookup order (hashes ascending,
+    // their ids), built by wq_frames_set_worlds; the sender table (wq_ingest_set_peers): keys ascending
+    wq::DevBuf ing_word, ing_list, ing_ctrl, ing_whash, ing_wid, ing_phi, ing_plo, ing_pid;
+    uint32_t ing_n_peers = 0;
+    int64_t ing_list_cap = -1;  // wq_debug_set_ingest_list (negative: the default)
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -397,6 +403,14 @@ int frames_set_worlds(wq_router* h, const char* names, const uint32_t* name_offs
 int launch_frames_build(wq_router* h, const wq_frames_src* src, size_t n_msgs, uint8_t* d_frames, size_t capacity_bytes,
                         uint64_t* d_frame_offsets, uint32_t* d_frame_size, wq_frames_counters* d_counters);
 void frames_release(wq_router* h);
+// wq_decode.hip: the world table's lookup order (enqueued on the stream by frames_set_worlds between its
+// two waits; off is rebased to 0), the sender table, the decoder on device arrays (asynchronous), and
+// the release of all three.
+int ingest_set_world_index(wq_router* h, const uint8_t* names, const uint32_t* off, uint32_t n_worlds);
+int ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, uint32_t n);
+int launch_frames_decode(wq_router* h, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
+                         size_t n_frame_bytes, const wq_ingest_out* out, wq_ingest_counters* d_counters);
+void ingest_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
 // wq_table_export.hip: frees the export's scratch.

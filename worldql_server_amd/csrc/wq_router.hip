@@ -129,6 +129,7 @@ int wq_router_destroy(wq_router* h) {
     rotate_release(h);
     pack_release(h);
     frames_release(h);
+    ingest_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -787,6 +788,30 @@ int wq_frames_build_device(wq_router* h, const wq_frames_src* src, size_t n_msgs
     if (n_msgs >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "frames_build: n_msgs must be < 2^32 - 1");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_frames_build(h, src, n_msgs, d_frames, capacity_bytes, d_frame_offsets, d_frame_size, d_counters);
+}
+
+int wq_ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, uint32_t n) {
+    if (!h) return WQ_E_INVALID;
+    if (n && !uuids) return set_error(h, WQ_E_INVALID, "ingest_set_peers: uuids is null");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return ingest_set_peers(h, uuids, ids, n);
+}
+
+int wq_frames_decode_device(wq_router* h, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
+                            size_t n_frame_bytes, const wq_ingest_out* out, wq_ingest_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!out) return set_error(h, WQ_E_INVALID, "frames_decode: out is null");
+    if ((n_frames && !d_frame_offsets) || (n_frame_bytes && !d_frames))
+        return set_error(h, WQ_E_INVALID, "frames_decode: a null array with a non-zero size");
+    if (n_frames >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "frames_decode: n_frames must be < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_frames_decode(h, d_frames, d_frame_offsets, n_frames, n_frame_bytes, out, d_counters);
+}
+
+int wq_debug_set_ingest_list(wq_router* h, int64_t entries) {
+    if (!h || entries > 0x7FFFFFFFll) return WQ_E_INVALID;
+    h->ing_list_cap = entries < 0 ? -1 : entries;
+    return WQ_OK;
 }
 
 // The argument rules both forms of wq_csr_diff share (capacities already clamped to 2^32 - 1).

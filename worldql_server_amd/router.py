@@ -85,6 +85,9 @@ def load_library(build_if_missing: bool = True):
         "wq_peer_pack_device": ([vp, vp, vp, u32, sz, vp, vp, sz, sz, u32, vp, sz, vp, vp, vp], i32),
         "wq_frames_set_worlds": ([vp, vp, vp, u32], i32),
         "wq_frames_build_device": ([vp, ctypes.POINTER(abi.FramesSrc), sz, vp, sz, vp, vp, vp], i32),
+        "wq_ingest_set_peers": ([vp, vp, vp, u32], i32),
+        "wq_frames_decode_device": ([vp, vp, vp, sz, sz, ctypes.POINTER(abi.IngestOut), vp], i32),
+        "wq_debug_set_ingest_list": ([vp, ctypes.c_int64], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -472,6 +475,37 @@ class Router:
         self._check(self.lib.wq_frames_build_device(self.h, ctypes.byref(src), n_msgs, frames_ptr or None,
                                                     capacity_bytes, frame_offsets_ptr or None, frame_size_ptr or None,
                                                     counters_ptr or None))
+
+    # ---- ingest: received frames decoded on the device (include/wq_router.h; host definition: ingest.py) ----
+    def set_ingest_peers(self, uuids, ids=None) -> None:
+        """wq_ingest_set_peers: the handle's table sender uuid -> peer id (uuids: n x 16 bytes, a list of
+        uuid.UUID or of 16-byte strings; ids: u32 per uuid, None: the index; empty clears it). A uuid that
+        occurs twice raises WQError (WQ_E_INVALID) and the old table stays. The table is copied; the call
+        waits for the handle's stream."""
+        from .ingest import uuid_rows
+        u = uuid_rows(uuids)
+        i = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+        if i is not None and len(i) != len(u):
+            raise ValueError("ids: one per uuid")
+        self._check(self.lib.wq_ingest_set_peers(self.h, u.ctypes.data if len(u) else None,
+                                                 i.ctypes.data if i is not None and len(i) else None, len(u)))
+
+    def decode_frames_device(self, frames_ptr: int | None, frame_offsets_ptr: int | None, n_frames: int,
+                             n_frame_bytes: int, out: "abi.IngestOut", counters_ptr: int | None = None) -> None:
+        """wq_frames_decode_device: n_frames received frames (frames_ptr[fo[i] .. fo[i + 1]), u64
+        offsets) verified and decoded as codec.decode_packed does, with world ids (set_worlds' table) and
+        peer ids (set_ingest_peers' table) resolved, into the device arrays of `out` (abi.IngestOut, each
+        nullable): pos / world / sender / repl are route_device's inputs. Asynchronous on the handle's
+        stream; the counters (abi.INGEST_COUNTERS_DTYPE) stay where counters_ptr points. Host definition:
+        ingest.decode_frames_np."""
+        self._check(self.lib.wq_frames_decode_device(self.h, frames_ptr or None, frame_offsets_ptr or None, n_frames,
+                                                     n_frame_bytes, ctypes.byref(out) if out is not None else None,
+                                                     counters_ptr or None))
+
+    def set_ingest_list(self, entries: int) -> None:
+        """wq_debug_set_ingest_list: a test hook, the long-string work list's capacity (0: none; negative:
+        the default). Results are identical for every value."""
+        self._check(self.lib.wq_debug_set_ingest_list(self.h, entries))
 
     # ---- interest changes between two ticks (include/wq_router.h; host reference: interest.py) ----
     def csr_diff(self, old_offsets, old_peers, new_offsets, new_peers, with_left: bool = True,
