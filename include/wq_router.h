@@ -1190,6 +1190,146 @@ int wq_frames_decode_device(wq_router* h, const uint8_t* d_frames, const uint64_
                             size_t n_frames, size_t n_frame_bytes,
                             const wq_ingest_out* out, wq_ingest_counters* d_counters /* nullable */);
 
+/* ---- ingest dispatch: a decoded tick split by instruction on the device ----
+ * wq_frames_decode_device leaves pos / world / sender / repl / instruction / flags for every frame of a
+ * tick, whatever its instruction. The reference dispatches one message at a time on the host
+ * (processing/thread.rs:72-108: heartbeats at once, the subscription task in order, the database task in
+ * order) and its handlers drop what they drop; processing.SubscriptionProcessor.process_tick restates
+ * that as a Python loop. Here one call takes the decode's arrays and writes, in arrival order, the
+ * compact inputs of wq_route_tick_device, wq_route_global_device and wq_apply_ops_device, the frame
+ * indices the host must see, and the table of runs that says in which order to issue those calls.
+ * Nothing is read back until the counters and the run table. An extension like the decoder.
+ *
+ * Classes (out->cls[i]; the first rule that matches decides)
+ *   "@global" means flag bit 4. "World resolved" means flag bit 5 AND world < WQ_WORLD_GLOBAL. "Sender
+ *   known" means flag bit 6 AND sender != 0xFFFFFFFF. "Position" means flag bit 1.
+ *   - WQ_CLS_BAD        flag bit 0 clear: the frame did not decode. Nothing else of it is looked at.
+ *   - WQ_CLS_HEARTBEAT  instruction 0 (thread.rs:76-81). Listed in side_src. With in->last_seen given and
+ *                       a known sender < n_last_seen, last_seen[sender] = now: a plain store, every
+ *                       writer writes the same value, so the result is deterministic.
+ *   - WQ_CLS_LOCAL      instruction 7, not "@global", position, world resolved (local_message.rs:17-56
+ *                       passed). One row in l_*: the frame index, the position copied as bits, world,
+ *                       sender, repl.
+ *   - WQ_CLS_GLOBAL     instruction 6, not "@global", world resolved (global_message.rs:37-54 passed).
+ *                       One row in g_*.
+ *   - WQ_CLS_BCAST      instruction 6 to "@global": the PeerMap broadcast of global_message.rs:18-35.
+ *                       Listed in side_src, the host's to send.
+ *   - WQ_CLS_OP         instruction 4 or 5, not "@global", position, world resolved, sender known
+ *                       (area_subscribe.rs:17-46, area_unsubscribe.rs passed). One wq_op: world, peer =
+ *                       sender, kind WQ_OP_SUBSCRIBE / WQ_OP_UNSUBSCRIBE, key_is_raw 0, pad_ zero, the
+ *                       position as bits; op_src holds its frame index.
+ *   - WQ_CLS_DEFERRED   instruction 4 with a position, not "@global", whose world or sender did not
+ *                       resolve: a join. The host interns the world or assigns the id. Listed in side_src.
+ *   - WQ_CLS_DB         instructions 8, 9, 11 (thread.rs:96-104). Listed in arrival order; the record path
+ *                       is the caller's.
+ *   - WQ_CLS_OTHER      instructions 1, 2, 3, 10, 12, 255 and any other byte. Listed; the reference
+ *                       panics or warns (thread.rs:83-94, 136).
+ *   - WQ_CLS_DROPPED    what the reference's handlers drop silently: Local / Subscribe / Unsubscribe to
+ *                       "@global"; Local / Subscribe / Unsubscribe without a position; a Local or Global
+ *                       whose world did not resolve (sanitize error or "no subscriptions in this world");
+ *                       an Unsubscribe whose world or sender did not resolve (a peer without an id holds
+ *                       nothing).
+ *   - A decoded frame whose flag and value disagree (bit 5 against world < WQ_WORLD_GLOBAL, bit 4 against
+ *     world == WQ_WORLD_GLOBAL, bit 6 against sender != 0xFFFFFFFF) sets error bit 0, and what disagrees
+ *     counts as unresolved. The input arrays are the caller's and may hold anything: an emitted wq_op
+ *     never carries a reserved world or the no-peer id (wq_apply_ops_device refuses a whole batch for one
+ *     such op), and a LocalMessage or GlobalMessage row whose sender is not known carries 0xFFFFFFFF, as
+ *     SubscriptionProcessor._sender_id passes it.
+ *   - The class counts sum to n_frames.
+ * Rows
+ *   - l_*, g_*, ops / op_src hold their class's frames in ascending frame index; side_src holds five
+ *     lists one behind the other — heartbeat | "@global" broadcast | database | other | deferred — each
+ *     ascending, side_begin[k] .. side_begin[k + 1] of the counters. Every row array has room for
+ *     n_frames rows; only [0, count) of each is written.
+ * Runs
+ *   - Only OP frames (table events) and LOCAL / GLOBAL frames (read events) are effective. A run is a
+ *     maximal stretch of effective frames of one kind, every other class ignored: process_tick's batching
+ *     with the events that have no effect left out, so there are never more runs than there. A dropped
+ *     event neither reads nor changes the table, so leaving it out of the rule changes no outcome.
+ *   - runs[r] = { kind (WQ_RUN_TABLE / WQ_RUN_READ), the run's first frame, where its rows begin in l_*,
+ *     g_* and ops }. Run r's rows end where run r + 1's begin; runs[n_runs] closes the table with kind
+ *     WQ_RUN_END, first_frame = n_frames and the three totals. Rows are stable, so a run's rows are
+ *     contiguous. With n_runs + 1 > runs_capacity the first runs_capacity entries are written and overflow
+ *     bit 0 is set.
+ *   - The caller reads the counters and the run table once, then issues in run order
+ *     wq_apply_ops_device(ops + op_begin, count) for a table run, and wq_route_tick_device /
+ *     wq_route_global_device on slices of l_* / g_* for a read run. The route kernels read their inputs
+ *     with scalar element loads at natural alignment, so a slice that begins at any row is a valid input
+ *     (tests/test_gpu_ingest_dispatch.py pins it).
+ *   - With n_deferred == 0 the outcome equals the reference's sequential loop. With deferred joins it is
+ *     exact for every frame before first_deferred; the caller either accepts that the joiners' events take
+ *     effect one tick later, or updates its tables and dispatches the suffix again. A deferred frame
+ *     whose world name the host then finds refused by the sanitizer is dropped there, as
+ *     area_subscribe.rs:23-33 drops it; it never had an effect, so it does not limit what is exact.
+ *   - Disconnects arrive on another channel (remove_rx, thread.rs:124-125) and stay wq_remove_peers
+ *     between ticks.
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. Three launches, no lane waits for
+ *     another: classify (one lane per frame; a summary per block of 1,024 frames), scan (one block over
+ *     the block summaries; it writes the counters and the closing run), emit (every lane places its row at
+ *     its block's base + the frames of its class below it). n_frames == 0 runs the scan alone and writes
+ *     the counters and the closing run only. Deterministic byte for byte.
+ *   - Nothing is written outside [0, count) of each array, [0, min(n_runs + 1, runs_capacity)) of runs and
+ *     the counters; the inputs are never written, apart from last_seen. Arrays are at their element's
+ *     natural alignment (pos, l_pos, ops 8 bytes; the u32 arrays and runs 4).
+ *   - Scratch lives in the handle, grow-only: n_frames bytes and 60 bytes per 1,024 frames. A steady-state
+ *     call does no hipMalloc, and the call alternates freely with decode, route, apply, budget, builder
+ *     and pack on one handle.
+ *   - WQ_E_INVALID, with nothing launched, for a null handle, in or out, a null required array with
+ *     n_frames > 0, runs null with runs_capacity > 0 and n_frames >= 2^32 - 1.
+ *   - A multi-GPU handle runs the call on its own stream with the arrays on devices[0]. */
+#define WQ_CLS_BAD 0
+#define WQ_CLS_HEARTBEAT 1
+#define WQ_CLS_LOCAL 2
+#define WQ_CLS_GLOBAL 3
+#define WQ_CLS_BCAST 4
+#define WQ_CLS_OP 5
+#define WQ_CLS_DEFERRED 6
+#define WQ_CLS_DB 7
+#define WQ_CLS_OTHER 8
+#define WQ_CLS_DROPPED 9
+#define WQ_CLS_COUNT 10
+
+#define WQ_RUN_END 0
+#define WQ_RUN_TABLE 1
+#define WQ_RUN_READ 2
+
+typedef struct wq_dispatch_in {      /* device pointers: the arrays wq_frames_decode_device wrote */
+    const uint8_t*  instruction;     /* [n] required */
+    const uint8_t*  flags;           /* [n] required: bits 0 - 6 of wq_ingest_out.flags */
+    const uint32_t* world;           /* [n] required */
+    const uint32_t* sender;          /* [n] required */
+    const uint8_t*  repl;            /* [n] required */
+    const double*   pos;             /* [3 n] required */
+    uint32_t*       last_seen;       /* [n_last_seen] nullable: heartbeat stamps, see above */
+    uint32_t        n_last_seen, now;
+} wq_dispatch_in;            /* 64 bytes */
+
+typedef struct wq_dispatch_run { uint32_t kind, first_frame, l_begin, g_begin, op_begin; } wq_dispatch_run; /* 20 B */
+
+typedef struct wq_dispatch_out {     /* device pointers, each nullable; every row array holds n_frames rows */
+    uint8_t*  cls;                   /* [n] the class of every frame (WQ_CLS_*) */
+    uint32_t* l_src; double* l_pos; uint32_t* l_world; uint32_t* l_sender; uint8_t* l_repl;  /* LocalMessage rows */
+    uint32_t* g_src; uint32_t* g_world; uint32_t* g_sender; uint8_t* g_repl;                 /* GlobalMessage rows */
+    wq_op*    ops;   uint32_t* op_src;                                                       /* table ops */
+    uint32_t* side_src;              /* [n] heartbeat | @global broadcast | database | other | deferred, each ascending */
+    wq_dispatch_run* runs; uint32_t runs_capacity;   /* runs[0 .. min(n_runs + 1, capacity)) incl. the closing entry */
+    uint32_t pad_;
+} wq_dispatch_out;           /* 120 bytes */
+
+typedef struct wq_dispatch_counters {
+    uint64_t n_frames;
+    uint64_t n_bad, n_heartbeat, n_local, n_global, n_bcast, n_op, n_deferred, n_db, n_other, n_dropped; /* per WQ_CLS_* */
+    uint64_t n_runs;
+    uint64_t side_begin[6];  /* the starts of the five lists inside side_src, and the end */
+    uint64_t first_deferred; /* the frame index of the first deferred event; n_frames when there is none */
+    uint64_t overflow;       /* bit 0: n_runs + 1 > runs_capacity */
+    uint64_t error;          /* bit 0: a flag and its value disagree */
+} wq_dispatch_counters;      /* 168 bytes */
+
+int wq_ingest_dispatch_device(wq_router* h, const wq_dispatch_in* in, size_t n_frames,
+                              const wq_dispatch_out* out, wq_dispatch_counters* d_counters /* nullable */);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

@@ -125,6 +125,41 @@ class IngestOut(ctypes.Structure):  # struct wq_ingest_out: device pointers, eac
 
 assert ctypes.sizeof(IngestOut) == 72 and INGEST_COUNTERS_DTYPE.itemsize == 64
 
+# ---- ingest dispatch (wq_ingest_dispatch_device) ----
+# WQ_CLS_*: the class of a frame, in the order of wq_dispatch_counters' per-class counts
+(CLS_BAD, CLS_HEARTBEAT, CLS_LOCAL, CLS_GLOBAL, CLS_BCAST, CLS_OP, CLS_DEFERRED, CLS_DB, CLS_OTHER,
+ CLS_DROPPED) = range(10)
+CLS_NAMES = ("bad", "heartbeat", "local", "global", "bcast", "op", "deferred", "db", "other", "dropped")
+RUN_END, RUN_TABLE, RUN_READ = 0, 1, 2          # WQ_RUN_*: wq_dispatch_run.kind
+DISPATCH_SIDE_LISTS = (CLS_HEARTBEAT, CLS_BCAST, CLS_DB, CLS_OTHER, CLS_DEFERRED)  # side_src's lists in order
+DISPATCH_ERROR_DISAGREE = 1                     # wq_dispatch_counters.error bit 0: a flag and its value disagree
+DISPATCH_OVERFLOW_RUNS = 1                      # wq_dispatch_counters.overflow bit 0: n_runs + 1 > runs_capacity
+# struct wq_dispatch_run: 20 bytes
+DISPATCH_RUN_DTYPE = np.dtype([("kind", np.uint32), ("first_frame", np.uint32), ("l_begin", np.uint32),
+                               ("g_begin", np.uint32), ("op_begin", np.uint32)])
+# struct wq_dispatch_counters: 168 bytes
+DISPATCH_COUNTERS_DTYPE = np.dtype([("n_frames", np.uint64)] + [("n_" + k, np.uint64) for k in CLS_NAMES] +
+                                   [("n_runs", np.uint64), ("side_begin", np.uint64, (6,)), ("first_deferred", np.uint64),
+                                    ("overflow", np.uint64), ("error", np.uint64)])
+
+
+class DispatchIn(ctypes.Structure):  # struct wq_dispatch_in: device pointers
+    _fields_ = [(k, ctypes.c_void_p) for k in ("instruction", "flags", "world", "sender", "repl", "pos", "last_seen")] + \
+               [("n_last_seen", ctypes.c_uint32), ("now", ctypes.c_uint32)]
+
+
+DISPATCH_OUT_ARRAYS = ("cls", "l_src", "l_pos", "l_world", "l_sender", "l_repl", "g_src", "g_world", "g_sender", "g_repl",
+                       "ops", "op_src", "side_src", "runs")
+
+
+class DispatchOut(ctypes.Structure):  # struct wq_dispatch_out: device pointers, each nullable
+    _fields_ = [(k, ctypes.c_void_p) for k in DISPATCH_OUT_ARRAYS] + [("runs_capacity", ctypes.c_uint32),
+                                                                      ("pad_", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(DispatchIn) == 64 and ctypes.sizeof(DispatchOut) == 120
+assert DISPATCH_RUN_DTYPE.itemsize == 20 and DISPATCH_COUNTERS_DTYPE.itemsize == 168
+
 
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]

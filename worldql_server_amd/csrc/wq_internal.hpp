@@ -274,6 +274,9 @@ struct wq_router {
     wq::DevBuf ing_word, ing_list, ing_ctrl, ing_whash, ing_wid, ing_phi, ing_plo, ing_pid;
     uint32_t ing_n_peers = 0;
     int64_t ing_list_cap = -1;  // wq_debug_set_ingest_list (negative: the default)
+    // ingest dispatch (wq_dispatch.hip): per frame its class between the passes; one DspSum per 1,024
+    // frames and the total behind them
+    wq::DevBuf dsp_cls, dsp_sum;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -411,6 +414,10 @@ int ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, ui
 int launch_frames_decode(wq_router* h, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
                          size_t n_frame_bytes, const wq_ingest_out* out, wq_ingest_counters* d_counters);
 void ingest_release(wq_router* h);
+// wq_dispatch.hip: the dispatch on device arrays (asynchronous) and the release of its scratch.
+int launch_ingest_dispatch(wq_router* h, const wq_dispatch_in* in, size_t n_frames, const wq_dispatch_out* out,
+                           wq_dispatch_counters* d_counters);
+void dispatch_release(wq_router* h);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
 // wq_table_export.hip: frees the export's scratch.

@@ -130,6 +130,7 @@ int wq_router_destroy(wq_router* h) {
     pack_release(h);
     frames_release(h);
     ingest_release(h);
+    dispatch_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -806,6 +807,18 @@ int wq_frames_decode_device(wq_router* h, const uint8_t* d_frames, const uint64_
     if (n_frames >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "frames_decode: n_frames must be < 2^32 - 1");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_frames_decode(h, d_frames, d_frame_offsets, n_frames, n_frame_bytes, out, d_counters);
+}
+
+int wq_ingest_dispatch_device(wq_router* h, const wq_dispatch_in* in, size_t n_frames, const wq_dispatch_out* out,
+                              wq_dispatch_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!in || !out) return set_error(h, WQ_E_INVALID, "ingest_dispatch: in or out is null");
+    if (n_frames && (!in->instruction || !in->flags || !in->world || !in->sender || !in->repl || !in->pos))
+        return set_error(h, WQ_E_INVALID, "ingest_dispatch: a null array with a non-zero size");
+    if (out->runs_capacity && !out->runs) return set_error(h, WQ_E_INVALID, "ingest_dispatch: runs is null");
+    if (n_frames >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_dispatch: n_frames must be < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_ingest_dispatch(h, in, n_frames, out, d_counters);
 }
 
 int wq_debug_set_ingest_list(wq_router* h, int64_t entries) {

@@ -8,6 +8,12 @@ sanitizer (world_names.py), the world table, the sender table — plus the flags
 `Router.set_ingest_peers` / `Router.decode_frames_device` (router.py) are the device call's bindings,
 `abi.IngestOut` and `abi.INGEST_COUNTERS_DTYPE` its structs. `IngestTick` keeps the device arrays of a
 tick and hands them to `Router.route_device` with nothing read back in between.
+
+`dispatch_np` is the definition of what wq_ingest_dispatch_device writes (csrc/wq_dispatch.hip): the
+classes of the header's table, the compact rows, the side lists and the run table, in plain Python over
+the dict `decode_frames_np` returns. `IngestTick.dispatch` enqueues the device call on the decode's
+arrays and `IngestTick.process` reads the counters and the run table, the tick's one read-back, and
+issues the runs in order.
 """
 from __future__ import annotations
 
@@ -157,11 +163,113 @@ def decode_frames_np(data, offsets, world_names, peer_uuids, peer_ids=None, n_fr
     return out
 
 
+DISPATCH_ROWS = ("cls", "l_src", "l_pos", "l_world", "l_sender", "l_repl", "g_src", "g_world", "g_sender", "g_repl",
+                 "ops", "op_src", "side_src")
+_INS_HEARTBEAT, _INS_SUBSCRIBE, _INS_UNSUBSCRIBE, _INS_GLOBAL, _INS_LOCAL = 0, 4, 5, 6, 7
+_INS_DB = (8, 9, 11)   # RecordCreate, RecordRead, RecordDelete
+
+
+def classify_frame(ins: int, flags: int, world: int, sender: int):
+    """(class, error bits) of one decoded frame: the table of include/wq_router.h, "ingest dispatch"."""
+    if not flags & OK:
+        return abi.CLS_BAD, 0
+    at_global = bool(flags & WORLD_IS_GLOBAL)
+    err = 0
+    if bool(flags & WORLD_KNOWN) != (world < abi.WORLD_GLOBAL) or at_global != (world == abi.WORLD_GLOBAL) or \
+            bool(flags & SENDER_KNOWN) != (sender != NO_PEER):
+        err = abi.DISPATCH_ERROR_DISAGREE
+    has_pos = bool(flags & HAS_POSITION)
+    world_ok = bool(flags & WORLD_KNOWN) and world < abi.WORLD_GLOBAL
+    sender_ok = bool(flags & SENDER_KNOWN) and sender != NO_PEER
+    if ins == _INS_HEARTBEAT:
+        cls = abi.CLS_HEARTBEAT
+    elif ins == _INS_LOCAL:        # local_message.rs:17-56
+        cls = abi.CLS_LOCAL if not at_global and has_pos and world_ok else abi.CLS_DROPPED
+    elif ins == _INS_GLOBAL:       # global_message.rs:18-54
+        cls = abi.CLS_BCAST if at_global else abi.CLS_GLOBAL if world_ok else abi.CLS_DROPPED
+    elif ins == _INS_SUBSCRIBE:    # area_subscribe.rs:17-46; an unresolved world or sender is a join
+        cls = abi.CLS_DROPPED if at_global or not has_pos else abi.CLS_OP if world_ok and sender_ok else abi.CLS_DEFERRED
+    elif ins == _INS_UNSUBSCRIBE:  # area_unsubscribe.rs; a peer without an id holds nothing
+        cls = abi.CLS_OP if not at_global and has_pos and world_ok and sender_ok else abi.CLS_DROPPED
+    elif ins in _INS_DB:
+        cls = abi.CLS_DB
+    else:
+        cls = abi.CLS_OTHER
+    return cls, err
+
+
+def dispatch_np(decoded, runs_capacity=None, last_seen=None, now=0):
+    """The definition of wq_ingest_dispatch_device over the dict decode_frames_np returns (instruction,
+    flags, world, sender, repl, pos): a dict of cls u8[n], the LocalMessage rows l_src / l_pos (f64[k, 3],
+    the bits copied) / l_world / l_sender / l_repl, the GlobalMessage rows g_*, ops (abi.OP_DTYPE) /
+    op_src, side_src (heartbeat | "@global" broadcast | database | other | deferred), runs
+    (abi.DISPATCH_RUN_DTYPE: the first min(n_runs + 1, runs_capacity) entries, the closing one included;
+    runs_capacity None: n_runs + 1), counters (a dict of abi.DISPATCH_COUNTERS_DTYPE's fields) and
+    last_seen (a stamped copy of the argument, or None)."""
+    ins_a, flags_a = np.asarray(decoded["instruction"], np.uint8), np.asarray(decoded["flags"], np.uint8)
+    world_a, sender_a = np.asarray(decoded["world"], np.uint32), np.asarray(decoded["sender"], np.uint32)
+    repl_a = np.asarray(decoded["repl"], np.uint8)
+    pos_a = np.ascontiguousarray(decoded["pos"], np.float64).reshape(-1, 3).view(np.uint64)   # bits, not values
+    n = len(ins_a)
+    seen = None if last_seen is None else np.array(last_seen, dtype=np.uint32, copy=True)
+    cls = np.zeros(n, np.uint8)
+    rows = {c: [] for c in range(len(abi.CLS_NAMES))}
+    runs, error, prev = [], 0, abi.RUN_END
+    for i in range(n):
+        c, e = classify_frame(int(ins_a[i]), int(flags_a[i]), int(world_a[i]), int(sender_a[i]))
+        cls[i] = c
+        error |= e
+        kind = abi.RUN_TABLE if c == abi.CLS_OP else abi.RUN_READ if c in (abi.CLS_LOCAL, abi.CLS_GLOBAL) else abi.RUN_END
+        if kind != abi.RUN_END and kind != prev:   # a run: a maximal stretch of effective frames of one kind
+            runs.append((kind, i, len(rows[abi.CLS_LOCAL]), len(rows[abi.CLS_GLOBAL]), len(rows[abi.CLS_OP])))
+            prev = kind
+        rows[c].append(i)
+    runs.append((abi.RUN_END, n, len(rows[abi.CLS_LOCAL]), len(rows[abi.CLS_GLOBAL]), len(rows[abi.CLS_OP])))
+    n_runs = len(runs) - 1
+
+    def row_sender(idx):
+        known = (flags_a[idx] & SENDER_KNOWN).astype(bool) & (sender_a[idx] != NO_PEER)
+        return np.where(known, sender_a[idx], np.uint32(NO_PEER)).astype(np.uint32)
+
+    ix = {c: np.array(v, dtype=np.int64) for c, v in rows.items()}
+    li, gi, oi = ix[abi.CLS_LOCAL], ix[abi.CLS_GLOBAL], ix[abi.CLS_OP]
+    ops = np.zeros(len(oi), dtype=abi.OP_DTYPE)
+    ops["world"], ops["peer"] = world_a[oi], sender_a[oi]
+    ops["kind"] = np.where(ins_a[oi] == _INS_SUBSCRIBE, abi.OP_SUBSCRIBE, abi.OP_UNSUBSCRIBE)
+    ops["key"] = pos_a[oi].view(np.int64)
+    hb = ix[abi.CLS_HEARTBEAT]
+    if seen is not None and len(hb):
+        s = row_sender(hb)
+        seen[s[s < len(seen)]] = now
+    side = [ix[c] for c in abi.DISPATCH_SIDE_LISTS]
+    cap = n_runs + 1 if runs_capacity is None else int(runs_capacity)
+    cnt = {"n_frames": n, "n_runs": n_runs}
+    cnt.update({"n_" + k: len(ix[c]) for c, k in enumerate(abi.CLS_NAMES)})
+    cnt["side_begin"] = [int(v) for v in np.concatenate([[0], np.cumsum([len(v) for v in side])])]
+    cnt["first_deferred"] = int(ix[abi.CLS_DEFERRED][0]) if len(ix[abi.CLS_DEFERRED]) else n
+    cnt["overflow"] = abi.DISPATCH_OVERFLOW_RUNS if n_runs + 1 > cap else 0
+    cnt["error"] = error
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)  # noqa: E731
+    return dict(cls=cls, l_src=u32(li), l_pos=pos_a[li].view(np.float64), l_world=world_a[li], l_sender=row_sender(li),
+                l_repl=repl_a[li], g_src=u32(gi), g_world=world_a[gi], g_sender=row_sender(gi), g_repl=repl_a[gi],
+                ops=ops, op_src=u32(oi), side_src=u32(np.concatenate(side)) if n else u32([]),
+                runs=np.array(runs[:min(n_runs + 1, cap)], dtype=abi.DISPATCH_RUN_DTYPE).reshape(-1),
+                counters=cnt, last_seen=seen)
+
+
+def dispatch_counters(raw) -> dict:
+    """abi.DISPATCH_COUNTERS_DTYPE bytes as dispatch_np's counters dict."""
+    c = np.asarray(raw).view(np.uint8)[:abi.DISPATCH_COUNTERS_DTYPE.itemsize].view(abi.DISPATCH_COUNTERS_DTYPE)[0]
+    return {k: [int(v) for v in c[k]] if k == "side_begin" else int(c[k]) for k in abi.DISPATCH_COUNTERS_DTYPE.names}
+
+
 class IngestTick:
     """The device arrays of one tick's decode, grow-only, and the step from received frames to
     Router.route_device: decode(frames, offsets) enqueues wq_frames_decode_device, route(...) the tick on
     the arrays it left, and nothing is read back or waited for between the two. read() is for tests and
-    for the host's share of the tick (the counters, the unknown senders' uuids)."""
+    for the host's share of the tick (the counters, the unknown senders' uuids). A tick that is more than
+    entity updates goes decode(...), dispatch(...), process(...): route() treats every frame as a
+    LocalMessage, the dispatch splits them by instruction and process() issues the runs in order."""
 
     _SPEC = dict(msg=(72, np.uint8), pos=(24, np.uint8), world=(4, np.uint8), sender=(4, np.uint8), repl=(1, np.uint8),
                  instruction=(1, np.uint8), sender_uuid=(16, np.uint8), flex_range=(8, np.uint8), flags=(1, np.uint8))
@@ -212,3 +320,132 @@ class IngestTick:
                     instruction=raw["instruction"], sender_uuid=raw["sender_uuid"].reshape(n, 16),
                     flex_range=raw["flex_range"].view(np.uint32).reshape(n, 2), flags=raw["flags"],
                     counters={k: int(c[k]) for k in INGEST_COUNTERS_DTYPE.names if k != "pad_"})
+
+    # ---- the dispatch: the decoded tick split by instruction (wq_ingest_dispatch_device) ----
+    _DSPEC = dict(cls=1, l_src=4, l_pos=24, l_world=4, l_sender=4, l_repl=1, g_src=4, g_world=4, g_sender=4, g_repl=1,
+                  ops=40, op_src=4, side_src=4)
+    _DTYPES = dict(cls=np.uint8, l_src=np.uint32, l_pos=np.float64, l_world=np.uint32, l_sender=np.uint32, l_repl=np.uint8,
+                   g_src=np.uint32, g_world=np.uint32, g_sender=np.uint32, g_repl=np.uint8, ops=abi.OP_DTYPE,
+                   op_src=np.uint32, side_src=np.uint32)
+    _DCOUNT = dict(cls="n_frames", l_src="n_local", l_pos="n_local", l_world="n_local", l_sender="n_local", l_repl="n_local",
+                   g_src="n_global", g_world="n_global", g_sender="n_global", g_repl="n_global", ops="n_op", op_src="n_op")
+    RUNS_FIRST_READ = 4096   # run entries process() reads back with the counters; a longer table takes a second read
+
+    def _grow_dispatch(self, n: int, runs_capacity: int) -> None:
+        import torch
+        if n > getattr(self, "dcap", 0) or not hasattr(self, "dbuf"):
+            self.dcap = max(n, 2 * getattr(self, "dcap", 0), 1)
+            # empty, not zeros: a fill would run on torch's stream, beside the call on the handle's
+            self.dbuf = {k: torch.empty(max(self.dcap * w, 8), dtype=torch.uint8, device=self.device)
+                         for k, w in self._DSPEC.items()}
+        if runs_capacity > getattr(self, "runs_cap", -1):
+            self.runs_cap = max(runs_capacity, 2 * getattr(self, "runs_cap", 0))
+            # the counters and the run table in one buffer: process() reads both with one copy
+            self.dctrl = torch.empty(abi.DISPATCH_COUNTERS_DTYPE.itemsize + 20 * max(self.runs_cap, 1), dtype=torch.uint8,
+                                     device=self.device)
+
+    def dispatch(self, runs_capacity: int | None = None, last_seen=None, now: int = 0) -> "IngestTick":
+        """Enqueues wq_ingest_dispatch_device on the arrays decode() left; nothing is read back. The rows, the
+        side lists, the run table (runs_capacity entries, default n + 1: every table fits) and the counters
+        stay on the device, grow-only beside the decode's. last_seen: a uint32 device tensor the heartbeats
+        stamp with `now`."""
+        n = self.n
+        self._grow_dispatch(n, n + 1 if runs_capacity is None else runs_capacity)
+        self.d_runs_capacity = n + 1 if runs_capacity is None else runs_capacity
+        o = self.out
+        self.d_in = abi.DispatchIn(instruction=o.instruction, flags=o.flags, world=o.world, sender=o.sender, repl=o.repl,
+                                   pos=o.pos, last_seen=None if last_seen is None else last_seen.data_ptr(),
+                                   n_last_seen=0 if last_seen is None else last_seen.numel(), now=now)
+        csize = abi.DISPATCH_COUNTERS_DTYPE.itemsize
+        self.d_out = abi.DispatchOut(**{k: t.data_ptr() for k, t in self.dbuf.items()},
+                                     runs=self.dctrl.data_ptr() + csize if self.d_runs_capacity else None,
+                                     runs_capacity=self.d_runs_capacity)
+        self.router.dispatch_device(self.d_in, n, self.d_out, self.dctrl.data_ptr())
+        return self
+
+    def _read_ctrl(self):
+        """The counters and the run table: one copy for tables of up to RUNS_FIRST_READ entries. Waits for
+        the device first, as read() does: the handle's stream is not torch's."""
+        import torch
+        torch.cuda.synchronize()
+        csize = abi.DISPATCH_COUNTERS_DTYPE.itemsize
+        first = min(self.d_runs_capacity, self.RUNS_FIRST_READ)
+        raw = self.dctrl[:csize + 20 * first].cpu().numpy()
+        cnt = dispatch_counters(raw)
+        have = min(cnt["n_runs"] + 1, self.d_runs_capacity)
+        if have > first:
+            raw = self.dctrl[:csize + 20 * have].cpu().numpy()
+        return cnt, raw[csize:csize + 20 * have].copy().view(abi.DISPATCH_RUN_DTYPE)
+
+    def process(self, offsets, peers, route_counters=None):
+        """Reads the counters and the run table (the tick's one read-back) and issues the runs in order on the
+        router: Router.apply_ops_device on a table run's slice of the ops, Router.route_device and
+        Router.route_global_device on a read run's slices of the LocalMessage and GlobalMessage rows.
+
+        offsets, peers: the caller's CSR buffers, int32 device tensors. Every route call gets its own
+        region of both, beginning at a multiple of four entries: rows + 1 offsets, and rows * K pairs, K =
+        what `peers` holds beyond the alignment, divided evenly by the tick's rows. route_counters
+        (nullable): a uint8 device tensor of 24 bytes per call (abi.COUNTERS_DTYPE), in call order.
+
+        Returns (counters, runs, reads): the dispatch's counters, the run table, and per read run a dict of
+        run, first_frame and, under "local" and "global", None or a dict of rows (begin, end in l_* / g_*),
+        offsets (the region's first entry), peers (its first pair), capacity and call (its index in
+        route_counters)."""
+        cnt, runs = self._read_ctrl()
+        if cnt["overflow"] & abi.DISPATCH_OVERFLOW_RUNS:
+            raise ValueError(f"the run table holds {self.d_runs_capacity} entries, the tick needs {cnt['n_runs'] + 1}")
+        spans = []
+        for a, b in zip(runs[:-1], runs[1:]):
+            if a["kind"] == abi.RUN_READ:
+                spans += [s for s in ((int(a["l_begin"]), int(b["l_begin"])), (int(a["g_begin"]), int(b["g_begin"]))) if s[1] > s[0]]
+        rows = cnt["n_local"] + cnt["n_global"]
+        if offsets.numel() < rows + 4 * len(spans):
+            raise ValueError(f"offsets: {rows + 4 * len(spans)} entries needed")
+        per_row = max(peers.numel() - 4 * len(spans), 0) // max(rows, 1)
+        if route_counters is not None and route_counters.numel() < 24 * len(spans):
+            raise ValueError(f"route_counters: {24 * len(spans)} bytes needed")
+        r, o = self.router, self.d_out
+        at = dict(o=0, p=0, call=0)
+
+        def region(lo, hi):
+            n = hi - lo
+            d = dict(rows=(lo, hi), offsets=at["o"], peers=at["p"], capacity=n * per_row, call=at["call"])
+            at["o"] += -(-(n + 1) // 4) * 4
+            at["p"] += -(-(n * per_row) // 4) * 4
+            at["call"] += 1
+            return d
+
+        reads = []
+        for k, (a, nxt) in enumerate(zip(runs[:-1], runs[1:])):
+            if a["kind"] == abi.RUN_TABLE:
+                lo, hi = int(a["op_begin"]), int(nxt["op_begin"])
+                r.apply_ops_device(o.ops + 40 * lo, hi - lo)
+                continue
+            read = dict(run=k, first_frame=int(a["first_frame"]), local=None, **{"global": None})
+            lo, hi = int(a["l_begin"]), int(nxt["l_begin"])
+            if hi > lo:
+                d = read["local"] = region(lo, hi)
+                r.route_device(o.l_pos + 24 * lo, o.l_world + 4 * lo, o.l_sender + 4 * lo, o.l_repl + lo, hi - lo,
+                               offsets.data_ptr() + 4 * d["offsets"], peers.data_ptr() + 4 * d["peers"], None, d["capacity"],
+                               None if route_counters is None else route_counters.data_ptr() + 24 * d["call"])
+            lo, hi = int(a["g_begin"]), int(nxt["g_begin"])
+            if hi > lo:
+                d = read["global"] = region(lo, hi)
+                r.route_global_device(o.g_world + 4 * lo, o.g_sender + 4 * lo, o.g_repl + lo, hi - lo,
+                                      offsets.data_ptr() + 4 * d["offsets"], peers.data_ptr() + 4 * d["peers"], None,
+                                      d["capacity"], None if route_counters is None else route_counters.data_ptr() + 24 * d["call"])
+            reads.append(read)
+        return cnt, runs, reads
+
+    def read_dispatch(self) -> dict:
+        """Every output of the dispatch and the counters as numpy arrays shaped like dispatch_np's
+        (synchronizes; for tests and for the host's share of the tick: the side lists)."""
+        import torch
+        torch.cuda.synchronize()
+        cnt, runs = self._read_ctrl()
+        got = dict(counters=cnt, runs=runs)
+        for k, w in self._DSPEC.items():
+            rows = cnt["side_begin"][5] if k == "side_src" else cnt[self._DCOUNT[k]]
+            a = self.dbuf[k][:rows * w].cpu().numpy().view(self._DTYPES[k])
+            got[k] = a.reshape(rows, 3) if k == "l_pos" else a
+        return got

@@ -88,6 +88,7 @@ def load_library(build_if_missing: bool = True):
         "wq_ingest_set_peers": ([vp, vp, vp, u32], i32),
         "wq_frames_decode_device": ([vp, vp, vp, sz, sz, ctypes.POINTER(abi.IngestOut), vp], i32),
         "wq_debug_set_ingest_list": ([vp, ctypes.c_int64], i32),
+        "wq_ingest_dispatch_device": ([vp, ctypes.POINTER(abi.DispatchIn), sz, ctypes.POINTER(abi.DispatchOut), vp], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -501,6 +502,18 @@ class Router:
         self._check(self.lib.wq_frames_decode_device(self.h, frames_ptr or None, frame_offsets_ptr or None, n_frames,
                                                      n_frame_bytes, ctypes.byref(out) if out is not None else None,
                                                      counters_ptr or None))
+
+    def dispatch_device(self, src: "abi.DispatchIn", n_frames: int, out: "abi.DispatchOut",
+                        counters_ptr: int | None = None) -> None:
+        """wq_ingest_dispatch_device: the decode's arrays (abi.DispatchIn: instruction, flags, world, sender,
+        repl, pos; last_seen / n_last_seen / now for the heartbeat stamps) split by instruction into the
+        device arrays of `out` (abi.DispatchOut, each nullable): the rows of route_device (l_*),
+        route_global_device (g_*) and apply_ops_device (ops), the side lists, and the run table that says
+        in which order to issue them. Asynchronous on the handle's stream; the counters
+        (abi.DISPATCH_COUNTERS_DTYPE) stay where counters_ptr points. Host definition: ingest.dispatch_np."""
+        self._check(self.lib.wq_ingest_dispatch_device(self.h, ctypes.byref(src) if src is not None else None, n_frames,
+                                                       ctypes.byref(out) if out is not None else None,
+                                                       counters_ptr or None))
 
     def set_ingest_list(self, entries: int) -> None:
         """wq_debug_set_ingest_list: a test hook, the long-string work list's capacity (0: none; negative:
