@@ -22,7 +22,7 @@ SOURCES = ["wq_route.hip", "wq_global.hip", "wq_query.hip", "wq_table.hip", "wq_
 HOST_SOURCES = ["wq_codec.cpp"]
 CXX = os.environ.get("CXX", "g++")
 HOST_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-pthread", "-Wall"]
-HEADERS = ["lane_xchg.hpp", "wq_device.hpp", "wq_internal.hpp", "route_common.hpp", "route_count.hpp", "route_scan.hpp", "route_emit.hpp", "route_tick.hpp", "route_radius.hpp", "route_spill.hpp", "route_gather.hpp", "table_prims.hpp", "follow_ops.hpp", "csr_diff_ops.hpp", "peer_major_ops.hpp", "budget_ops.hpp", "rotate_ops.hpp", "pack_ops.hpp", "frame_ops.hpp", "decode_ops.hpp", "dispatch_ops.hpp", "record_ops.hpp", "export_ops.hpp", "route_async.hpp", "shard_ctx.hpp"]
+HEADERS = ["lane_xchg.hpp", "wq_device.hpp", "wq_internal.hpp", "route_common.hpp", "route_count.hpp", "route_scan.hpp", "route_emit.hpp", "route_tick.hpp", "route_radius.hpp", "route_spill.hpp", "route_gather.hpp", "table_prims.hpp", "send_rows.hpp", "follow_ops.hpp", "csr_diff_ops.hpp", "peer_major_ops.hpp", "budget_ops.hpp", "rotate_ops.hpp", "pack_ops.hpp", "frame_ops.hpp", "decode_ops.hpp", "dispatch_ops.hpp", "record_ops.hpp", "export_ops.hpp", "route_async.hpp", "shard_ctx.hpp"]
 # No fast-math and no FMA contraction: coord_clamp must reproduce Rust's f64 op sequence.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]

@@ -33,7 +33,7 @@ constexpr int kBudDigitBits = 8;
 constexpr uint32_t kBudBins = 1u << kBudDigitBits;
 constexpr int kBudPasses = 64 / kBudDigitBits;
 // A histogram pass counts a tile of kBudTile ordinals that lie in one row in LDS; a block takes
-// kBudTiles tiles (wq_budget.hip k_bud_hist).
+// kBudTiles tiles (wq_budget.hip k_sel_hist).
 constexpr uint32_t kBudTile = 256;
 constexpr uint32_t kBudTiles = 8;
 constexpr uint64_t kBudInf = 0x7FF0000000000000ull;  // the bits of +infinity
@@ -164,6 +164,11 @@ __host__ __device__ __forceinline__ bool bud_keeps(uint64_t key, uint32_t tie_ra
     return key < thr_key || (key == thr_key && tie_rank < thr_ties);
 }
 
+// The flag of position x in a granule's flag words.
+__host__ __device__ __forceinline__ bool flag_at(const uint64_t* __restrict__ words, uint64_t x) {
+    return (words[x >> 6] >> (x & 63u)) & 1ull;
+}
+
 // Bits set below position x in a granule's flag words: prefix base[] + popcount (x < 64 * granules).
 __host__ __device__ __forceinline__ uint32_t bud_before(const uint32_t* __restrict__ base,
                                                         const uint64_t* __restrict__ words, uint32_t x) {
@@ -212,7 +217,7 @@ __host__ __device__ __forceinline__ uint64_t bud_byte_term(const uint32_t* __res
                                                            const uint64_t* __restrict__ words, uint32_t T,
                                                            uint64_t q) {
     if (q >= T) return 0;
-    if (words && !((words[q >> 6] >> (q & 63u)) & 1ull)) return 0;
+    if (words && !flag_at(words, q)) return 0;
     return size[q];
 }
 

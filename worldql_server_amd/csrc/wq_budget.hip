@@ -6,7 +6,7 @@
 // does not have (it routes and forgets: local_message.rs:52-86, peer_map.rs:151-163).
 //
 //   rows    one lane per peer: the clamped length; a saturating scan gives the ordinal space
-//           (budget_ops.hpp); a second lane per peer: class, kept count, the select's slot of a long
+//           (send_rows.hpp); a second lane per peer: class, kept count, the select's slot of a long
 //           cut row; the scan of the kept counts is the output's offsets
 //   keys    one lane per ordinal: its row (a search over the prefix), its key (two position gathers),
 //           its row's class
@@ -23,10 +23,11 @@
 // most kBudShort key reads. Placement comes from counts and prefix sums alone; the atomics are
 // integer adds into histograms and counters, so the output is the same bytes every time.
 //
-// The byte budgets (wq_peer_budget_bytes_device: the nearest messages that fit in W bytes) follow the
-// count budget below and share its rows, keys, flag words and emit.
+// The byte budgets (wq_peer_budget_bytes_device: the nearest messages that fit in W bytes) share the
+// rows, keys, flag words and emit, and the select: its kernels are written once and take what a key
+// weighs, and everything that follows from it, from a policy (SelCount, SelBytes).
 #include "budget_ops.hpp"
-#include "table_prims.hpp"
+#include "send_rows.hpp"
 
 namespace wq {
 
@@ -34,77 +35,117 @@ namespace {
 
 static_assert(kBudTile == kBlock && kBudBins == kBlock, "a histogram tile is one block of lanes, one lane per bin");
 
+// What both budgets read and work on; CntIn / CntWs and BytIn / BytWs add each one's own.
 struct BudIn {
     const uint32_t* off;
     const uint32_t* msgs;
     const double* mpos;
     const double* ppos;
-    const uint32_t* budget;
-    uint32_t n_peers, n_in, n_msgs, n_ppos, k;
+    uint32_t n_peers, n_in, n_msgs, n_ppos;
 };
 
 struct BudWs {
-    uint32_t* len;    // [n_peers + 1] clamped lengths, then the kept counts
+    uint32_t* len;    // [n_peers + 1] clamped lengths, then the kept counts (bytes: the rows' classes)
     uint32_t* sum;    // [n_peers + 1] their saturating prefix
     uint32_t* pre;    // [n_peers + 1] the prefix clamped to n_in: the ordinal space
     uint64_t* key;    // [n_in]
     uint32_t* row;    // [n_in]
     uint8_t* cls;     // [n_in]
-    BudSel* sel;      // [n_in / kBudShort + 1]
-    uint32_t* hist;   // kBudBins per slot; all zero between calls
     uint64_t* words;  // [2 * nG] tie flags, keep flags
     uint32_t* cnt;    // [2 * nG]
     uint32_t* base;   // [2 * nG]
-    uint32_t* ctrl;   // {rows_cut, error}
+    uint32_t* ctrl;   // {rows_cut, error}; bytes: behind them, as a u64, bytes_in
 };
 
-__global__ __launch_bounds__(kBlock) void k_bud_len(BudIn in, BudWs ws) {
-    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p > in.n_peers) return;
-    bool ok = true;
-    ws.len[p] = p < in.n_peers ? bud_len(in.off, (uint32_t)p, in.n_in, &ok) : 0u;
-    if (!ok) atomicOr(&ws.ctrl[1], kBudErrRows);
+struct CntIn : BudIn {
+    const uint32_t* budget;
+    uint32_t k;
+};
+
+struct CntWs : BudWs {
+    BudSel* sel;     // [n_in / kBudShort + 1]
+    uint32_t* hist;  // kBudBins per slot; all zero between calls
+};
+
+struct BytIn : BudIn {
+    const uint32_t* msize;
+    const uint64_t* wbudget;
+    uint64_t w;
+};
+
+struct BytWs : BudWs {
+    uint32_t* size;            // [n_in]
+    uint64_t* scan;            // [n_in + 1]
+    BudSelW* sel;              // [n_in / kBudShort + 1]
+    unsigned long long* hist;  // kBudBins per slot; all zero between calls
+};
+
+__host__ __device__ __forceinline__ RowSpace bud_rows(const BudIn& in, const BudWs& ws) {
+    return RowSpace{in.off, in.n_peers, in.n_in, ws.len, ws.sum, ws.pre};
 }
 
-__global__ __launch_bounds__(kBlock) void k_bud_rows(BudIn in, BudWs ws) {
-    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p > in.n_peers) return;
-    const uint32_t a = ws.sum[p] < in.n_in ? ws.sum[p] : in.n_in;
-    ws.pre[p] = a;
-    if (p == in.n_peers) {
-        ws.len[p] = 0;
-        return;
+// ---- the select's policies: what an element weighs, and what follows from it ----
+
+// The count budget: every key weighs 1, a row keeps its `need` smallest.
+struct SelCount {
+    using In = CntIn;
+    using Ws = CntWs;
+    using Sel = BudSel;
+    using Bin = uint32_t;
+    static __device__ __forceinline__ Bin weight(const Ws&, uint64_t) { return 1u; }
+    static __device__ __forceinline__ uint32_t& left(Sel& s) { return s.need; }
+    static __device__ __forceinline__ bool picks(Bin below, Bin count, Bin need) {
+        return bud_picks(below, count, need);
     }
-    const uint32_t b = ws.sum[p + 1] < in.n_in ? ws.sum[p + 1] : in.n_in;
-    const uint32_t len = b - a;
-    if (len != ws.len[p]) atomicOr(&ws.ctrl[1], kBudErrRows);  // overlapping rows: cut at n_in ordinals
-    const uint32_t B = bud_budget(in.budget, in.k, (uint32_t)p);
-    const uint8_t c = bud_class(len, B);
-    if (c != kBudAll) atomicAdd(&ws.ctrl[0], 1u);
-    if (c == kBudLongCut) ws.sel[a >> kBudShortLog2] = BudSel{0ull, B, 1u};
-    ws.len[p] = len < B ? len : B;
-}
+    static __device__ __forceinline__ bool short_keeps(const In& in, const Ws& ws, uint32_t p, uint32_t q) {
+        return bud_short_keeps(ws.key, ws.pre[p], ws.pre[p + 1] - ws.pre[p], q, bud_budget(in.budget, in.k, p));
+    }
+    // q0: the row's first ordinal; the tie flags and their prefix are in place
+    static __device__ __forceinline__ bool long_keeps(const Ws& ws, const Sel& s, uint32_t q0, uint32_t q,
+                                                      uint64_t key) {
+        uint32_t tie_rank = 0;
+        if (key == s.prefix) tie_rank = bud_before(ws.base, ws.words, q) - bud_before(ws.base, ws.words, q0);
+        return bud_keeps(key, tie_rank, s.prefix, s.need);
+    }
+};
 
-__global__ __launch_bounds__(kBlock) void k_bud_keys(BudIn in, BudWs ws) {
-    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= ws.pre[in.n_peers]) return;
-    const uint32_t p = bud_row_of(ws.pre, in.n_peers, (uint32_t)q);
-    const uint32_t j = bud_row_start(in.off, p, in.n_in) + ((uint32_t)q - ws.pre[p]);
-    bool bad;
-    ws.key[q] = bud_key(in.mpos, in.n_msgs, in.ppos, in.n_ppos, p, in.msgs[j], &bad);
-    ws.row[q] = p;
-    ws.cls[q] = bud_class(ws.pre[p + 1] - ws.pre[p], bud_budget(in.budget, in.k, p));
-    if (bad) atomicOr(&ws.ctrl[1], kBudErrMsg);
-}
+// The byte budgets: a key weighs its element's size (a zero weight adds nothing), a row keeps its
+// smallest while they fit in `remaining` bytes.
+struct SelBytes {
+    using In = BytIn;
+    using Ws = BytWs;
+    using Sel = BudSelW;
+    using Bin = unsigned long long;
+    static __device__ __forceinline__ Bin weight(const Ws& ws, uint64_t q) { return ws.size[q]; }
+    static __device__ __forceinline__ uint64_t& left(Sel& s) { return s.remaining; }
+    static __device__ __forceinline__ bool picks(Bin below, Bin bytes, Bin remaining) {
+        return bud_picks_bytes(below, bytes, remaining);
+    }
+    static __device__ __forceinline__ bool short_keeps(const In& in, const Ws& ws, uint32_t p, uint32_t q) {
+        return bud_short_keeps_bytes(ws.key, ws.size, ws.pre[p], ws.pre[p + 1] - ws.pre[p], q,
+                                     bud_wbudget(in.wbudget, in.w, p));
+    }
+    // q0: the row's first ordinal; ws.scan is the scan of the ties' sizes
+    static __device__ __forceinline__ bool long_keeps(const Ws& ws, const Sel& s, uint32_t q0, uint32_t q,
+                                                      uint64_t key) {
+        uint64_t tie_bytes = 0;
+        if (key == s.prefix) tie_bytes = ws.scan[q] - ws.scan[q0] + ws.size[q];
+        return bud_keeps_bytes(key, tie_bytes, s.prefix, s.remaining);
+    }
+};
 
-// One pass of the select's histograms. A tile of kBudTile ordinals inside one long cut row counts in
-// LDS; the bins go to the row's histogram when the block moves to another row or ends. Tiles that
-// hold a row boundary add to the rows' histograms directly, one global atomic per matching key: a
-// row of a few hundred elements then sends that many atomics, and in the top passes, where a row's
-// keys share their digit, to one address (rows of 257 to a few thousand elements mostly take this
-// path; it is where the C3 shape's time goes).
-__global__ __launch_bounds__(kBlock) void k_bud_hist(BudWs ws, uint32_t n_peers, int shift) {
-    __shared__ uint32_t bins[kBudBins];
+// ---- the kernels both budgets launch ----
+
+// One pass of the select's histograms. A tile of kBudTile ordinals inside one long cut row sums its
+// weights in LDS; the bins go to the row's histogram when the block moves to another row or ends.
+// Tiles that hold a row boundary add to the rows' histograms directly, one global atomic per matching
+// key: a row of a few hundred elements then sends that many atomics, and in the top passes, where a
+// row's keys share their digit, to one address (rows of 257 to a few thousand elements mostly take
+// this path; it is where the C3 shape's time goes).
+template <class P>
+__global__ __launch_bounds__(kBlock) void k_sel_hist(typename P::Ws ws, uint32_t n_peers, int shift) {
+    using Bin = typename P::Bin;
+    __shared__ Bin bins[kBudBins];
     const uint32_t T = ws.pre[n_peers];
     const uint32_t t = threadIdx.x;
     bins[t] = 0;
@@ -132,13 +173,15 @@ __global__ __launch_bounds__(kBlock) void k_bud_hist(BudWs ws, uint32_t n_peers,
             }
             if (q < T) {
                 const uint64_t key = ws.key[q];
-                if (bud_matches(key, cur_prefix, shift)) atomicAdd(&bins[bud_digit(key, shift)], 1u);
+                const Bin w = P::weight(ws, q);
+                if (w && bud_matches(key, cur_prefix, shift)) atomicAdd(&bins[bud_digit(key, shift)], w);
             }
         } else if (q < T && ws.cls[q] == kBudLongCut) {
             const uint32_t slot = ws.pre[ws.row[q]] >> kBudShortLog2;
             const uint64_t key = ws.key[q];
-            if (bud_matches(key, ws.sel[slot].prefix, shift))
-                atomicAdd(&ws.hist[(uint64_t)slot * kBudBins + bud_digit(key, shift)], 1u);
+            const Bin w = P::weight(ws, q);
+            if (w && bud_matches(key, ws.sel[slot].prefix, shift))
+                atomicAdd(&ws.hist[(uint64_t)slot * kBudBins + bud_digit(key, shift)], w);
         }
     }
     if (cur_slot != 0xFFFFFFFFu) {
@@ -147,36 +190,39 @@ __global__ __launch_bounds__(kBlock) void k_bud_hist(BudWs ws, uint32_t n_peers,
     }
 }
 
-// One block per slot: lane t owns bin t; the block's prefix sum finds the bin that holds the need-th
-// smallest matching key. The bins are read and zeroed, so the histograms are zero after every pass.
-__global__ __launch_bounds__(kBudBins) void k_bud_pick(BudWs ws, int shift) {
-    __shared__ uint32_t wave_tot[kBudBins / 64];
-    BudSel* s = ws.sel + blockIdx.x;
+// One block per slot: lane t owns bin t; the block's prefix sum finds the bin the policy picks: the
+// one that holds the need-th smallest matching key, or in which the running byte total first exceeds
+// what is left. The bins are read and zeroed, so the histograms are zero after every pass.
+template <class P>
+__global__ __launch_bounds__(kBudBins) void k_sel_pick(typename P::Ws ws, int shift) {
+    using Bin = typename P::Bin;
+    __shared__ Bin wave_tot[kBudBins / 64];
+    typename P::Sel* s = ws.sel + blockIdx.x;
     if (!s->active) return;  // block-uniform
-    const uint32_t need = s->need;
+    const Bin left = P::left(*s);
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    uint32_t* bin = ws.hist + (uint64_t)blockIdx.x * kBudBins + t;
-    const uint32_t c = *bin;
+    Bin* bin = ws.hist + (uint64_t)blockIdx.x * kBudBins + t;
+    const Bin c = *bin;
     *bin = 0;
-    uint32_t incl = c;
+    Bin incl = c;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
+        const Bin o = __shfl_up(incl, d);
         if (lane >= (uint32_t)d) incl += o;
     }
     if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();  // also: every lane has read s->need
-    uint32_t below = incl - c;
+    __syncthreads();  // also: every lane has read what is left
+    Bin below = incl - c;
     for (uint32_t w = 0; w < wave; ++w) below += wave_tot[w];
-    if (bud_picks(below, c, need)) {
+    if (P::picks(below, c, left)) {
         s->prefix |= (uint64_t)t << shift;
-        s->need = need - below;
+        P::left(*s) = left - below;
     }
 }
 
 // flags 0: ties (long cut rows, key == the row's threshold key); flags 1: keep.
-template <int kKeep>
-__global__ __launch_bounds__(kBlock) void k_bud_flag(BudIn in, BudWs ws, uint32_t nG) {
+template <class P, int kKeep>
+__global__ __launch_bounds__(kBlock) void k_sel_flag(typename P::In in, typename P::Ws ws, uint32_t nG) {
     const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint32_t g = (uint32_t)(q >> 6);
     if (g >= nG) return;  // wave-uniform
@@ -189,34 +235,54 @@ __global__ __launch_bounds__(kBlock) void k_bud_flag(BudIn in, BudWs ws, uint32_
         } else if (c == kBudAll) {
             f = true;
         } else if (c == kBudShortCut) {
-            const uint32_t p = ws.row[q];
-            f = bud_short_keeps(ws.key, ws.pre[p], ws.pre[p + 1] - ws.pre[p], (uint32_t)q,
-                                bud_budget(in.budget, in.k, p));
+            f = P::short_keeps(in, ws, ws.row[q], (uint32_t)q);
         } else if (c == kBudLongCut) {
             const uint32_t q0 = ws.pre[ws.row[q]];
-            const BudSel s = ws.sel[q0 >> kBudShortLog2];
-            const uint64_t key = ws.key[q];
-            uint32_t tie_rank = 0;
-            if (key == s.prefix) tie_rank = bud_before(ws.base, ws.words, (uint32_t)q) - bud_before(ws.base, ws.words, q0);
-            f = bud_keeps(key, tie_rank, s.prefix, s.need);
+            const typename P::Sel s = ws.sel[q0 >> kBudShortLog2];
+            f = P::long_keeps(ws, s, q0, (uint32_t)q, ws.key[q]);
         }
     }
-    const uint64_t word = __ballot(f);
-    if ((threadIdx.x & 63u) == 0) {
-        ws.words[(uint64_t)kKeep * nG + g] = word;
-        ws.cnt[(uint64_t)kKeep * nG + g] = (uint32_t)__popcll(word);
-    }
+    store_flags(ws.words, ws.cnt, (uint64_t)kKeep * nG + g, f);
 }
 
 __global__ __launch_bounds__(kBlock) void k_bud_emit(BudIn in, BudWs ws, uint32_t nG, uint32_t* __restrict__ out) {
     const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (q >= ws.pre[in.n_peers]) return;
     const uint64_t* words = ws.words + nG;
-    if (!((words[q >> 6] >> (q & 63u)) & 1ull)) return;
-    const uint32_t p = ws.row[q];
-    const uint32_t j = bud_row_start(in.off, p, in.n_in) + ((uint32_t)q - ws.pre[p]);
+    if (!flag_at(words, q)) return;
+    const uint32_t j = rows_elem(in.off, ws.pre, in.n_in, ws.row[q], (uint32_t)q);
     const uint32_t pos = bud_before(ws.base + nG, words, (uint32_t)q);
     if (pos < in.n_in) out[pos] = in.msgs[j];
+}
+
+// ---- the count budget's own ----
+
+__global__ __launch_bounds__(kBlock) void k_bud_rows(CntIn in, CntWs ws) {
+    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p > in.n_peers) return;
+    uint32_t len;
+    const uint32_t a = rows_pre_step(bud_rows(in, ws), p, &ws.ctrl[1], kBudErrRows, &len);
+    if (p == in.n_peers) {
+        ws.len[p] = 0;
+        return;
+    }
+    const uint32_t B = bud_budget(in.budget, in.k, (uint32_t)p);
+    const uint8_t c = bud_class(len, B);
+    if (c != kBudAll) atomicAdd(&ws.ctrl[0], 1u);
+    if (c == kBudLongCut) ws.sel[a >> kBudShortLog2] = BudSel{0ull, B, 1u};
+    ws.len[p] = len < B ? len : B;
+}
+
+__global__ __launch_bounds__(kBlock) void k_bud_keys(CntIn in, CntWs ws) {
+    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= ws.pre[in.n_peers]) return;
+    const uint32_t p = bud_row_of(ws.pre, in.n_peers, (uint32_t)q);
+    const uint32_t j = rows_elem(in.off, ws.pre, in.n_in, p, (uint32_t)q);
+    bool bad;
+    ws.key[q] = bud_key(in.mpos, in.n_msgs, in.ppos, in.n_ppos, p, in.msgs[j], &bad);
+    ws.row[q] = p;
+    ws.cls[q] = bud_class(ws.pre[p + 1] - ws.pre[p], bud_budget(in.budget, in.k, p));
+    if (bad) atomicOr(&ws.ctrl[1], kBudErrMsg);
 }
 
 __global__ void k_bud_counters(BudWs ws, uint32_t n_peers, const uint32_t* __restrict__ out_off,
@@ -229,26 +295,17 @@ __global__ void k_bud_counters(BudWs ws, uint32_t n_peers, const uint32_t* __res
     *counters = c;
 }
 
-int scan_sat(wq_router* h, const uint32_t* in, uint32_t* out, size_t n) {
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
-    return WQ_OK;
-}
-
-// ---- byte budgets: of every peer's send list the nearest messages that fit in W bytes ----
+// ---- the byte budgets' own: of every peer's send list the nearest messages that fit in W bytes ----
 //
-// The same ordinal space, keys, flag words and emit; the select is weighted: its histograms sum the
-// sizes of the matching keys (u64 bins) and a pick takes the bin in which the running byte total
-// first exceeds what is left of W. The output's offsets are not known before the elements are, so
-// they come from the keep words.
+// The select is weighted: its histograms sum the sizes of the matching keys (u64 bins) and a pick
+// takes the bin in which the running byte total first exceeds what is left of W. The output's offsets
+// are not known before the elements are, so they come from the keep words.
 //
-//   rows    k_bud_len and the saturating scan as above; k_byt_pre: the ordinal space
+//   rows    k_rows_len, the saturating scan and k_rows_pre: the ordinal space
 //   keys    one lane per ordinal: its row, key and size; a u64 scan of the sizes (S)
 //   class   one lane per peer: the row's total S[pre[p + 1]] - S[pre[p]] against W_p gives its class
 //           and seeds a long cut row's slot; one lane per ordinal copies its row's class
-//   select  as above with sizes: k_byt_hist / k_byt_pick, kBudPasses times
+//   select  as above with sizes, kBudPasses times
 //   ties    the ballot of "key == the row's threshold key"; a u64 scan of the ties' sizes
 //   keep    the keep flags of every class; scan of the granules' counts
 //   offsets one lane per peer: the kept bits before pre[p]
@@ -257,188 +314,41 @@ int scan_sat(wq_router* h, const uint32_t* in, uint32_t* out, size_t n) {
 // The three u64 scans share one buffer: S is dead once the classes are known, the ties' scan once
 // the keep words are.
 
-struct BytIn {
-    BudIn b;  // budget and k unused
-    const uint32_t* msize;
-    const uint64_t* wbudget;
-    uint64_t w;
-};
-
-struct BytWs {
-    BudWs b;         // len: the rows' classes after k_byt_class; sel and hist unused
-    uint32_t* size;  // [n_in]
-    uint64_t* scan;  // [n_in + 1]
-    BudSelW* sel;    // [n_in / kBudShort + 1]
-    uint64_t* hist;  // kBudBins per slot; all zero between calls
-};
-
 // ctrl: {rows_cut, error} and, as a u64 behind them, bytes_in.
 __device__ __forceinline__ uint64_t* byt_bytes_in(uint32_t* ctrl) { return reinterpret_cast<uint64_t*>(ctrl + 2); }
 
-struct BytTerm {
-    const uint32_t* size;
-    const uint64_t* words;  // nullable
-    const uint32_t* T;
-    __host__ __device__ __forceinline__ uint64_t operator()(uint64_t q) const {
-        return bud_byte_term(size, words, *T, q);
-    }
-};
-
-__global__ __launch_bounds__(kBlock) void k_byt_pre(BudIn in, BudWs ws) {
-    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p > in.n_peers) return;
-    const uint32_t a = ws.sum[p] < in.n_in ? ws.sum[p] : in.n_in;
-    ws.pre[p] = a;
-    if (p == in.n_peers) return;
-    const uint32_t b = ws.sum[p + 1] < in.n_in ? ws.sum[p + 1] : in.n_in;
-    if (b - a != ws.len[p]) atomicOr(&ws.ctrl[1], kBudErrRows);  // overlapping rows: cut at n_in ordinals
-}
-
 __global__ __launch_bounds__(kBlock) void k_byt_keys(BytIn in, BytWs ws) {
     const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= ws.b.pre[in.b.n_peers]) return;
-    const uint32_t p = bud_row_of(ws.b.pre, in.b.n_peers, (uint32_t)q);
-    const uint32_t j = bud_row_start(in.b.off, p, in.b.n_in) + ((uint32_t)q - ws.b.pre[p]);
-    const uint32_t m = in.b.msgs[j];
+    if (q >= ws.pre[in.n_peers]) return;
+    const uint32_t p = bud_row_of(ws.pre, in.n_peers, (uint32_t)q);
+    const uint32_t m = in.msgs[rows_elem(in.off, ws.pre, in.n_in, p, (uint32_t)q)];
     bool bad;
-    ws.b.key[q] = bud_key(in.b.mpos, in.b.n_msgs, in.b.ppos, in.b.n_ppos, p, m, &bad);
-    ws.b.row[q] = p;
-    ws.size[q] = bud_size(in.msize, in.b.n_msgs, m);
-    if (bad) atomicOr(&ws.b.ctrl[1], kBudErrMsg);
+    ws.key[q] = bud_key(in.mpos, in.n_msgs, in.ppos, in.n_ppos, p, m, &bad);
+    ws.row[q] = p;
+    ws.size[q] = bud_size(in.msize, in.n_msgs, m);
+    if (bad) atomicOr(&ws.ctrl[1], kBudErrMsg);
 }
 
 __global__ __launch_bounds__(kBlock) void k_byt_class(BytIn in, BytWs ws) {
     const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p > in.b.n_peers) return;
-    const uint32_t a = ws.b.pre[p];
-    if (p == in.b.n_peers) {
-        *byt_bytes_in(ws.b.ctrl) = ws.scan[a];
+    if (p > in.n_peers) return;
+    const uint32_t a = ws.pre[p];
+    if (p == in.n_peers) {
+        *byt_bytes_in(ws.ctrl) = ws.scan[a];
         return;
     }
-    const uint32_t b = ws.b.pre[p + 1];
+    const uint32_t b = ws.pre[p + 1];
     const uint64_t W = bud_wbudget(in.wbudget, in.w, (uint32_t)p);
     const uint8_t c = bud_class_bytes(b - a, ws.scan[b] - ws.scan[a], W);
-    if (c != kBudAll) atomicAdd(&ws.b.ctrl[0], 1u);
+    if (c != kBudAll) atomicAdd(&ws.ctrl[0], 1u);
     if (c == kBudLongCut) ws.sel[a >> kBudShortLog2] = BudSelW{0ull, W, 1u, 0u};
-    ws.b.len[p] = c;
+    ws.len[p] = c;
 }
 
-__global__ __launch_bounds__(kBlock) void k_byt_cls(BytWs ws, uint32_t n_peers) {
+__global__ __launch_bounds__(kBlock) void k_byt_cls(BudWs ws, uint32_t n_peers) {
     const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= ws.b.pre[n_peers]) return;
-    ws.b.cls[q] = (uint8_t)ws.b.len[ws.b.row[q]];
-}
-
-// k_bud_hist with sizes: a tile inside one long cut row sums in LDS and flushes the bins it touched,
-// a tile with a row boundary adds to the rows' histograms directly. Zero-size elements add nothing.
-__global__ __launch_bounds__(kBlock) void k_byt_hist(BytWs ws, uint32_t n_peers, int shift) {
-    __shared__ unsigned long long bins[kBudBins];
-    unsigned long long* hist = reinterpret_cast<unsigned long long*>(ws.hist);
-    const uint32_t T = ws.b.pre[n_peers];
-    const uint32_t t = threadIdx.x;
-    bins[t] = 0;
-    __syncthreads();
-    uint32_t cur_slot = 0xFFFFFFFFu;
-    uint64_t cur_prefix = 0;
-    for (uint32_t i = 0; i < kBudTiles; ++i) {
-        const uint64_t q0 = ((uint64_t)blockIdx.x * kBudTiles + i) * kBudTile;
-        if (q0 >= T) break;  // block-uniform
-        const uint32_t last = T - q0 > kBudTile ? (uint32_t)q0 + kBudTile - 1 : T - 1;
-        const uint32_t r0 = ws.b.row[q0], r1 = ws.b.row[last];
-        const uint64_t q = q0 + t;
-        if (r0 == r1) {  // block-uniform: one row, one class
-            if (ws.b.cls[q0] != kBudLongCut) continue;
-            const uint32_t slot = ws.b.pre[r0] >> kBudShortLog2;
-            if (slot != cur_slot) {
-                if (cur_slot != 0xFFFFFFFFu) {
-                    __syncthreads();
-                    if (bins[t]) atomicAdd(&hist[(uint64_t)cur_slot * kBudBins + t], bins[t]);
-                    bins[t] = 0;
-                    __syncthreads();
-                }
-                cur_slot = slot;
-                cur_prefix = ws.sel[slot].prefix;
-            }
-            if (q < T) {
-                const uint64_t key = ws.b.key[q];
-                const uint32_t sz = ws.size[q];
-                if (sz && bud_matches(key, cur_prefix, shift))
-                    atomicAdd(&bins[bud_digit(key, shift)], (unsigned long long)sz);
-            }
-        } else if (q < T && ws.b.cls[q] == kBudLongCut) {
-            const uint32_t slot = ws.b.pre[ws.b.row[q]] >> kBudShortLog2;
-            const uint64_t key = ws.b.key[q];
-            const uint32_t sz = ws.size[q];
-            if (sz && bud_matches(key, ws.sel[slot].prefix, shift))
-                atomicAdd(&hist[(uint64_t)slot * kBudBins + bud_digit(key, shift)], (unsigned long long)sz);
-        }
-    }
-    if (cur_slot != 0xFFFFFFFFu) {
-        __syncthreads();
-        if (bins[t]) atomicAdd(&hist[(uint64_t)cur_slot * kBudBins + t], bins[t]);
-    }
-}
-
-// One block per slot: lane t owns bin t; the block's prefix sum finds the bin in which the running
-// byte total first exceeds what is left. The bins are read and zeroed.
-__global__ __launch_bounds__(kBudBins) void k_byt_pick(BytWs ws, int shift) {
-    __shared__ uint64_t wave_tot[kBudBins / 64];
-    BudSelW* s = ws.sel + blockIdx.x;
-    if (!s->active) return;  // block-uniform
-    const uint64_t remaining = s->remaining;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    uint64_t* bin = ws.hist + (uint64_t)blockIdx.x * kBudBins + t;
-    const uint64_t c = *bin;
-    *bin = 0;
-    uint64_t incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)incl, d);
-        if (lane >= (uint32_t)d) incl += o;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();  // also: every lane has read s->remaining
-    uint64_t below = incl - c;
-    for (uint32_t w = 0; w < wave; ++w) below += wave_tot[w];
-    if (bud_picks_bytes(below, c, remaining)) {
-        s->prefix |= (uint64_t)t << shift;
-        s->remaining = remaining - below;
-    }
-}
-
-// flags 0: ties (long cut rows, key == the row's threshold key); flags 1: keep. The keep pass reads
-// ws.scan as the scan of the ties' sizes.
-template <int kKeep>
-__global__ __launch_bounds__(kBlock) void k_byt_flag(BytIn in, BytWs ws, uint32_t nG) {
-    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t g = (uint32_t)(q >> 6);
-    if (g >= nG) return;  // wave-uniform
-    const uint32_t T = ws.b.pre[in.b.n_peers];
-    bool f = false;
-    if (q < T) {
-        const uint8_t c = ws.b.cls[q];
-        if (!kKeep) {
-            if (c == kBudLongCut) f = ws.b.key[q] == ws.sel[ws.b.pre[ws.b.row[q]] >> kBudShortLog2].prefix;
-        } else if (c == kBudAll) {
-            f = true;
-        } else if (c == kBudShortCut) {
-            const uint32_t p = ws.b.row[q];
-            f = bud_short_keeps_bytes(ws.b.key, ws.size, ws.b.pre[p], ws.b.pre[p + 1] - ws.b.pre[p], (uint32_t)q,
-                                      bud_wbudget(in.wbudget, in.w, p));
-        } else if (c == kBudLongCut) {
-            const uint32_t q0 = ws.b.pre[ws.b.row[q]];
-            const BudSelW s = ws.sel[q0 >> kBudShortLog2];
-            const uint64_t key = ws.b.key[q];
-            uint64_t tie_bytes = 0;
-            if (key == s.prefix) tie_bytes = ws.scan[q] - ws.scan[q0] + ws.size[q];
-            f = bud_keeps_bytes(key, tie_bytes, s.prefix, s.remaining);
-        }
-    }
-    const uint64_t word = __ballot(f);
-    if ((threadIdx.x & 63u) == 0) {
-        ws.b.words[(uint64_t)kKeep * nG + g] = word;
-        ws.b.cnt[(uint64_t)kKeep * nG + g] = (uint32_t)__popcll(word);
-    }
+    if (q >= ws.pre[n_peers]) return;
+    ws.cls[q] = (uint8_t)ws.len[ws.row[q]];
 }
 
 __global__ __launch_bounds__(kBlock) void k_byt_offsets(BudWs ws, uint32_t n_peers, uint32_t nG,
@@ -452,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_byt_offsets(BudWs ws, uint32_t n_pee
 __global__ __launch_bounds__(kBlock) void k_byt_out_bytes(BytWs ws, uint32_t n_peers, uint64_t* __restrict__ out_bytes) {
     const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n_peers) return;
-    out_bytes[p] = ws.scan[ws.b.pre[p + 1]] - ws.scan[ws.b.pre[p]];
+    out_bytes[p] = ws.scan[ws.pre[p + 1]] - ws.scan[ws.pre[p]];
 }
 
 // kept_scan: the scan of the kept sizes, NULL when the call has no element.
@@ -468,26 +378,60 @@ __global__ void k_byt_counters(BudWs ws, uint32_t n_peers, const uint32_t* __res
     *counters = c;
 }
 
-// Exclusive u64 scan of the n terms f(0 .. n).
-int scan_bytes(wq_router* h, const BytTerm& f, uint64_t* out, size_t n) {
-    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), f);
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                      h->stream));
+// ---- host side ----
+
+// The buffers both budgets run on, and the two views of them. The per-peer and per-ordinal arrays,
+// the flag words and ctrl are one set: the calls are ordered on the handle's stream and nothing in
+// them outlives a call. Each budget's select state and histograms, which must be zero between
+// calls, are its own.
+int bud_setup(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
+              const double* d_msg_pos, size_t n_msgs, const double* d_peer_pos, size_t n_peer_pos, BudIn* in,
+              BudWs* ws) {
+    const size_t nG = n_in / 64 + 1;
+    if (int rc = rows_alloc(h, (size_t)n_peers + 1)) return rc;
+    WQ_ALLOC(h, h->bud_key, n_in * 8);
+    WQ_ALLOC(h, h->bud_row, n_in * 4);
+    WQ_ALLOC(h, h->bud_cls, n_in);
+    WQ_ALLOC(h, h->bud_words, nG * 16);
+    WQ_ALLOC(h, h->bud_cnt, nG * 8);
+    WQ_ALLOC(h, h->bud_base, nG * 8);
+    WQ_ALLOC(h, h->bud_ctrl, 64);
+    const RowSpace r = rows_view(h, d_peer_offsets, n_peers, n_in);
+    *in = BudIn{d_peer_offsets, d_msgs, d_msg_pos, d_peer_pos, n_peers, r.n_in,
+                (uint32_t)std::min<size_t>(n_msgs, 0xFFFFFFFFull),
+                (uint32_t)std::min<size_t>(n_peer_pos, 0xFFFFFFFFull)};
+    *ws = BudWs{r.len, r.sum, r.pre, h->bud_key.as<uint64_t>(), h->bud_row.as<uint32_t>(), h->bud_cls.as<uint8_t>(),
+                h->bud_words.as<uint64_t>(), h->bud_cnt.as<uint32_t>(), h->bud_base.as<uint32_t>(),
+                h->bud_ctrl.as<uint32_t>()};
+    return WQ_OK;
+}
+
+// The select's kBudPasses pairs of a histogram pass and its pick, the top digit first.
+template <class P>
+int launch_select(wq_router* h, ZeroedBuf& hist, const typename P::Ws& ws, uint32_t n_peers, size_t n_in,
+                  size_t n_slots) {
+    hipStream_t s = h->stream;
+    const dim3 grid_h(grid_for((n_in + kBudTiles - 1) / kBudTiles));
+    const dim3 grid_p((unsigned)n_slots);
+    hist.begin();  // until every pass has its pick
+    for (int pass = 0; pass < kBudPasses; ++pass) {
+        hipLaunchKernelGGL(k_sel_hist<P>, grid_h, dim3(kBlock), 0, s, ws, n_peers, bud_shift(pass));
+        WQ_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(k_sel_pick<P>, grid_p, dim3(kBudBins), 0, s, ws, bud_shift(pass));
+        WQ_HIP(h, hipGetLastError());
+    }
+    hist.end();
     return WQ_OK;
 }
 
 }  // namespace
 
 void budget_release(wq_router* h) {
-    h->bud_hist_clean = 0;
-    h->byt_hist_clean = 0;
     for (DevBuf* b : {&h->bud_len, &h->bud_sum, &h->bud_pre, &h->bud_key, &h->bud_row, &h->bud_cls, &h->bud_sel,
-                      &h->bud_hist, &h->bud_words, &h->bud_cnt, &h->bud_base, &h->bud_ctrl, &h->byt_size, &h->byt_scan,
-                      &h->byt_sel, &h->byt_hist})
+                      &h->bud_words, &h->bud_cnt, &h->bud_base, &h->bud_ctrl, &h->byt_size, &h->byt_scan, &h->byt_sel})
         b->release();
+    h->bud_hist.release();
+    h->byt_hist.release();
 }
 
 // The call on device arrays (the handle's device is current; arguments validated, n_in <= 2^32 - 1,
@@ -500,43 +444,23 @@ int launch_peer_budget(wq_router* h, const uint32_t* d_peer_offsets, const uint3
     const size_t rows = (size_t)n_peers + 1;
     const size_t n_slots = n_in / kBudShort + 1;
     const uint32_t nG = (uint32_t)(n_in / 64 + 1);
-    WQ_ALLOC(h, h->bud_len, rows * 4);
-    WQ_ALLOC(h, h->bud_sum, rows * 4);
-    WQ_ALLOC(h, h->bud_pre, rows * 4);
-    WQ_ALLOC(h, h->bud_key, n_in * 8);
-    WQ_ALLOC(h, h->bud_row, n_in * 4);
-    WQ_ALLOC(h, h->bud_cls, n_in);
+    CntIn in;
+    CntWs ws;
+    if (int rc = bud_setup(h, d_peer_offsets, d_msgs, n_peers, n_in, d_msg_pos, n_msgs, d_peer_pos, n_peer_pos, &in,
+                           &ws))
+        return rc;
     WQ_ALLOC(h, h->bud_sel, n_slots * sizeof(BudSel));
-    WQ_ALLOC(h, h->bud_words, (size_t)nG * 16);
-    WQ_ALLOC(h, h->bud_cnt, (size_t)nG * 8);
-    WQ_ALLOC(h, h->bud_base, (size_t)nG * 8);
-    WQ_ALLOC(h, h->bud_ctrl, 64);
-    // The select needs every bin zero when a call starts. Every pick pass zeroes the bins it read, so
-    // a call that launched all its passes leaves them zero: bud_hist_clean is the number of bytes
-    // known to be zero. It is 0 for a new allocation (decided from the capacity, not the address:
-    // a freed block's address can come back) and while a call's passes are being launched, so a
-    // call that failed between a histogram pass and its pick makes the next one clear the buffer.
-    const size_t hist_cap = h->bud_hist.bytes;
-    WQ_ALLOC(h, h->bud_hist, n_slots * kBudBins * 4);
-    if (h->bud_hist.bytes != hist_cap) h->bud_hist_clean = 0;
-    if (h->bud_hist_clean < h->bud_hist.bytes) {
-        WQ_HIP(h, hipMemsetAsync(h->bud_hist.p, 0, h->bud_hist.bytes, s));
-        h->bud_hist_clean = h->bud_hist.bytes;
-    }
+    if (int rc = h->bud_hist.prepare(h, n_slots * kBudBins * 4, s)) return rc;
     WQ_HIP(h, hipMemsetAsync(h->bud_ctrl.p, 0, 64, s));
     WQ_HIP(h, hipMemsetAsync(h->bud_sel.p, 0, n_slots * sizeof(BudSel), s));
-
-    const BudIn in{d_peer_offsets, d_msgs,      d_msg_pos,         d_peer_pos,           d_budget,
-                   n_peers,        (uint32_t)n_in, (uint32_t)std::min<size_t>(n_msgs, 0xFFFFFFFFull),
-                   (uint32_t)std::min<size_t>(n_peer_pos, 0xFFFFFFFFull), k};
-    const BudWs ws{h->bud_len.as<uint32_t>(), h->bud_sum.as<uint32_t>(),  h->bud_pre.as<uint32_t>(),
-                   h->bud_key.as<uint64_t>(), h->bud_row.as<uint32_t>(),  h->bud_cls.as<uint8_t>(),
-                   h->bud_sel.as<BudSel>(),   h->bud_hist.as<uint32_t>(), h->bud_words.as<uint64_t>(),
-                   h->bud_cnt.as<uint32_t>(), h->bud_base.as<uint32_t>(), h->bud_ctrl.as<uint32_t>()};
+    in.budget = d_budget;
+    in.k = k;
+    ws.sel = h->bud_sel.as<BudSel>();
+    ws.hist = h->bud_hist.b.as<uint32_t>();
 
     const dim3 blk(kBlock);
     const dim3 grid_r(grid_for(rows));
-    hipLaunchKernelGGL(k_bud_len, grid_r, blk, 0, s, in, ws);
+    hipLaunchKernelGGL(k_rows_len, grid_r, blk, 0, s, bud_rows(in, ws), ws.ctrl + 1, kBudErrRows);
     WQ_HIP(h, hipGetLastError());
     if (int rc = scan_sat(h, ws.len, ws.sum, rows)) return rc;
     hipLaunchKernelGGL(k_bud_rows, grid_r, blk, 0, s, in, ws);
@@ -547,19 +471,11 @@ int launch_peer_budget(wq_router* h, const uint32_t* d_peer_offsets, const uint3
         const dim3 grid_g(grid_for((uint64_t)nG * 64));
         hipLaunchKernelGGL(k_bud_keys, grid_e, blk, 0, s, in, ws);
         WQ_HIP(h, hipGetLastError());
-        h->bud_hist_clean = 0;  // until every pass has its pick
-        for (int pass = 0; pass < kBudPasses; ++pass) {
-            hipLaunchKernelGGL(k_bud_hist, dim3(grid_for((n_in + kBudTiles - 1) / kBudTiles)), blk, 0, s, ws, n_peers,
-                               bud_shift(pass));
-            WQ_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_bud_pick, dim3((unsigned)n_slots), dim3(kBudBins), 0, s, ws, bud_shift(pass));
-            WQ_HIP(h, hipGetLastError());
-        }
-        h->bud_hist_clean = h->bud_hist.bytes;
-        hipLaunchKernelGGL(k_bud_flag<0>, grid_g, blk, 0, s, in, ws, nG);
+        if (int rc = launch_select<SelCount>(h, h->bud_hist, ws, n_peers, n_in, n_slots)) return rc;
+        hipLaunchKernelGGL((k_sel_flag<SelCount, 0>), grid_g, blk, 0, s, in, ws, nG);
         WQ_HIP(h, hipGetLastError());
         if (int rc = scan_u32(h, ws.cnt, ws.base, nG, false)) return rc;
-        hipLaunchKernelGGL(k_bud_flag<1>, grid_g, blk, 0, s, in, ws, nG);
+        hipLaunchKernelGGL((k_sel_flag<SelCount, 1>), grid_g, blk, 0, s, in, ws, nG);
         WQ_HIP(h, hipGetLastError());
         if (int rc = scan_u32(h, ws.cnt + nG, ws.base + nG, nG, false)) return rc;
         hipLaunchKernelGGL(k_bud_emit, grid_e, blk, 0, s, in, ws, nG, d_out_msgs);
@@ -573,9 +489,6 @@ int launch_peer_budget(wq_router* h, const uint32_t* d_peer_offsets, const uint3
 }
 
 // The byte budgets on device arrays (as launch_peer_budget: arguments validated, positions resolved).
-// The per-peer and per-ordinal arrays, the flag words and ctrl are the count budget's buffers: the
-// calls are ordered on the handle's stream and nothing in them outlives a call. The select's state
-// and histograms, which must be zero between calls, are this path's own.
 int launch_peer_budget_bytes(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
                              size_t n_in, const double* d_msg_pos, const uint32_t* d_msg_size, size_t n_msgs,
                              const double* d_peer_pos, size_t n_peer_pos, uint64_t w, const uint64_t* d_budget_bytes,
@@ -585,81 +498,57 @@ int launch_peer_budget_bytes(wq_router* h, const uint32_t* d_peer_offsets, const
     const size_t rows = (size_t)n_peers + 1;
     const size_t n_slots = n_in / kBudShort + 1;
     const uint32_t nG = (uint32_t)(n_in / 64 + 1);
-    WQ_ALLOC(h, h->bud_len, rows * 4);
-    WQ_ALLOC(h, h->bud_sum, rows * 4);
-    WQ_ALLOC(h, h->bud_pre, rows * 4);
-    WQ_ALLOC(h, h->bud_key, n_in * 8);
-    WQ_ALLOC(h, h->bud_row, n_in * 4);
-    WQ_ALLOC(h, h->bud_cls, n_in);
-    WQ_ALLOC(h, h->bud_words, (size_t)nG * 16);
-    WQ_ALLOC(h, h->bud_cnt, (size_t)nG * 8);
-    WQ_ALLOC(h, h->bud_base, (size_t)nG * 8);
-    WQ_ALLOC(h, h->bud_ctrl, 64);
+    BytIn in;
+    BytWs ws;
+    if (int rc = bud_setup(h, d_peer_offsets, d_msgs, n_peers, n_in, d_msg_pos, n_msgs, d_peer_pos, n_peer_pos, &in,
+                           &ws))
+        return rc;
     WQ_ALLOC(h, h->byt_size, n_in * 4);
     WQ_ALLOC(h, h->byt_scan, (n_in + 1) * 8);
     WQ_ALLOC(h, h->byt_sel, n_slots * sizeof(BudSelW));
-    // byt_hist_clean: as bud_hist_clean above, for this path's own histograms.
-    const size_t hist_cap = h->byt_hist.bytes;
-    WQ_ALLOC(h, h->byt_hist, n_slots * kBudBins * 8);
-    if (h->byt_hist.bytes != hist_cap) h->byt_hist_clean = 0;
-    if (h->byt_hist_clean < h->byt_hist.bytes) {
-        WQ_HIP(h, hipMemsetAsync(h->byt_hist.p, 0, h->byt_hist.bytes, s));
-        h->byt_hist_clean = h->byt_hist.bytes;
-    }
+    if (int rc = h->byt_hist.prepare(h, n_slots * kBudBins * 8, s)) return rc;
     WQ_HIP(h, hipMemsetAsync(h->bud_ctrl.p, 0, 64, s));
     WQ_HIP(h, hipMemsetAsync(h->byt_sel.p, 0, n_slots * sizeof(BudSelW), s));
-
-    const BytIn in{BudIn{d_peer_offsets, d_msgs, d_msg_pos, d_peer_pos, nullptr, n_peers, (uint32_t)n_in,
-                         (uint32_t)std::min<size_t>(n_msgs, 0xFFFFFFFFull),
-                         (uint32_t)std::min<size_t>(n_peer_pos, 0xFFFFFFFFull), 0u},
-                   d_msg_size, d_budget_bytes, w};
-    const BytWs ws{BudWs{h->bud_len.as<uint32_t>(), h->bud_sum.as<uint32_t>(), h->bud_pre.as<uint32_t>(),
-                         h->bud_key.as<uint64_t>(), h->bud_row.as<uint32_t>(), h->bud_cls.as<uint8_t>(), nullptr, nullptr,
-                         h->bud_words.as<uint64_t>(), h->bud_cnt.as<uint32_t>(), h->bud_base.as<uint32_t>(),
-                         h->bud_ctrl.as<uint32_t>()},
-                   h->byt_size.as<uint32_t>(), h->byt_scan.as<uint64_t>(), h->byt_sel.as<BudSelW>(),
-                   h->byt_hist.as<uint64_t>()};
+    in.msize = d_msg_size;
+    in.wbudget = d_budget_bytes;
+    in.w = w;
+    ws.size = h->byt_size.as<uint32_t>();
+    ws.scan = h->byt_scan.as<uint64_t>();
+    ws.sel = h->byt_sel.as<BudSelW>();
+    ws.hist = h->byt_hist.b.as<unsigned long long>();
 
     const dim3 blk(kBlock);
     const dim3 grid_r(grid_for(rows));
-    hipLaunchKernelGGL(k_bud_len, grid_r, blk, 0, s, in.b, ws.b);
+    hipLaunchKernelGGL(k_rows_len, grid_r, blk, 0, s, bud_rows(in, ws), ws.ctrl + 1, kBudErrRows);
     WQ_HIP(h, hipGetLastError());
-    if (int rc = scan_sat(h, ws.b.len, ws.b.sum, rows)) return rc;
-    hipLaunchKernelGGL(k_byt_pre, grid_r, blk, 0, s, in.b, ws.b);
+    if (int rc = scan_sat(h, ws.len, ws.sum, rows)) return rc;
+    hipLaunchKernelGGL(k_rows_pre, grid_r, blk, 0, s, bud_rows(in, ws), ws.ctrl + 1, kBudErrRows);
     WQ_HIP(h, hipGetLastError());
-    const uint32_t* d_T = ws.b.pre + n_peers;
+    const uint32_t* d_T = ws.pre + n_peers;
     const uint64_t* kept_scan = nullptr;
     if (n_in) {
         const dim3 grid_e(grid_for(n_in));
         const dim3 grid_g(grid_for((uint64_t)nG * 64));
         hipLaunchKernelGGL(k_byt_keys, grid_e, blk, 0, s, in, ws);
         WQ_HIP(h, hipGetLastError());
-        if (int rc = scan_bytes(h, BytTerm{ws.size, nullptr, d_T}, ws.scan, n_in + 1)) return rc;
+        if (int rc = scan_terms(h, SizeTerm{ws.size, nullptr, d_T}, ws.scan, n_in + 1)) return rc;
         hipLaunchKernelGGL(k_byt_class, grid_r, blk, 0, s, in, ws);
         WQ_HIP(h, hipGetLastError());
         hipLaunchKernelGGL(k_byt_cls, grid_e, blk, 0, s, ws, n_peers);
         WQ_HIP(h, hipGetLastError());
-        h->byt_hist_clean = 0;  // until every pass has its pick
-        for (int pass = 0; pass < kBudPasses; ++pass) {
-            hipLaunchKernelGGL(k_byt_hist, dim3(grid_for((n_in + kBudTiles - 1) / kBudTiles)), blk, 0, s, ws, n_peers,
-                               bud_shift(pass));
-            WQ_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_byt_pick, dim3((unsigned)n_slots), dim3(kBudBins), 0, s, ws, bud_shift(pass));
-            WQ_HIP(h, hipGetLastError());
-        }
-        h->byt_hist_clean = h->byt_hist.bytes;
-        hipLaunchKernelGGL(k_byt_flag<0>, grid_g, blk, 0, s, in, ws, nG);
+        if (int rc = launch_select<SelBytes>(h, h->byt_hist, ws, n_peers, n_in, n_slots)) return rc;
+        hipLaunchKernelGGL((k_sel_flag<SelBytes, 0>), grid_g, blk, 0, s, in, ws, nG);
         WQ_HIP(h, hipGetLastError());
-        if (int rc = scan_bytes(h, BytTerm{ws.size, ws.b.words, d_T}, ws.scan, n_in + 1)) return rc;
-        hipLaunchKernelGGL(k_byt_flag<1>, grid_g, blk, 0, s, in, ws, nG);
+        if (int rc = scan_terms(h, SizeTerm{ws.size, ws.words, d_T}, ws.scan, n_in + 1)) return rc;
+        hipLaunchKernelGGL((k_sel_flag<SelBytes, 1>), grid_g, blk, 0, s, in, ws, nG);
         WQ_HIP(h, hipGetLastError());
-        if (int rc = scan_u32(h, ws.b.cnt + nG, ws.b.base + nG, nG, false)) return rc;
-        hipLaunchKernelGGL(k_byt_offsets, grid_r, blk, 0, s, ws.b, n_peers, nG, d_out_offsets);
+        if (int rc = scan_u32(h, ws.cnt + nG, ws.base + nG, nG, false)) return rc;
+        hipLaunchKernelGGL(k_byt_offsets, grid_r, blk, 0, s, ws, n_peers, nG, d_out_offsets);
         WQ_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(k_bud_emit, grid_e, blk, 0, s, in.b, ws.b, nG, d_out_msgs);
+        hipLaunchKernelGGL(k_bud_emit, grid_e, blk, 0, s, in, ws, nG, d_out_msgs);
         WQ_HIP(h, hipGetLastError());
         if (d_out_bytes || d_counters) {
-            if (int rc = scan_bytes(h, BytTerm{ws.size, ws.b.words + nG, d_T}, ws.scan, n_in + 1)) return rc;
+            if (int rc = scan_terms(h, SizeTerm{ws.size, ws.words + nG, d_T}, ws.scan, n_in + 1)) return rc;
             kept_scan = ws.scan;
         }
         if (d_out_bytes && n_peers) {
@@ -671,7 +560,8 @@ int launch_peer_budget_bytes(wq_router* h, const uint32_t* d_peer_offsets, const
         if (d_out_bytes && n_peers) WQ_HIP(h, hipMemsetAsync(d_out_bytes, 0, (size_t)n_peers * 8, s));
     }
     if (d_counters) {
-        hipLaunchKernelGGL(k_byt_counters, dim3(1), dim3(1), 0, s, ws.b, n_peers, d_out_offsets, kept_scan, d_counters);
+        hipLaunchKernelGGL(k_byt_counters, dim3(1), dim3(1), 0, s, ws, n_peers, d_out_offsets, kept_scan,
+                           d_counters);
         WQ_HIP(h, hipGetLastError());
     }
     return WQ_OK;

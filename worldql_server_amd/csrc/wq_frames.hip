@@ -22,7 +22,7 @@
 // from the scan alone; the only atomics are ORs into the error word.
 #include "decode_ops.hpp"
 #include "frame_ops.hpp"
-#include "table_prims.hpp"
+#include "send_rows.hpp"
 
 namespace wq {
 
@@ -223,15 +223,7 @@ int launch_frames_build(wq_router* h, const wq_frames_src* src, size_t n_msgs, u
         hipLaunchKernelGGL(k_frames_size, dim3(grid_for(n_msgs)), dim3(kBlock), 0, s, in, size, d_frame_size, ctrl);
         WQ_HIP(h, hipGetLastError());
     }
-    {
-        auto it = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), FrameTerm{size, n_msgs});
-        size_t bytes = 0;
-        WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, it, d_frame_offsets, (uint64_t)0, n_msgs + 1,
-                                          rocprim::plus<uint64_t>(), s));
-        WQ_ALLOC(h, h->sort_tmp, bytes);
-        WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, it, d_frame_offsets, (uint64_t)0, n_msgs + 1,
-                                          rocprim::plus<uint64_t>(), s));
-    }
+    if (int rc = scan_terms(h, FrameTerm{size, n_msgs}, d_frame_offsets, n_msgs + 1)) return rc;
     if (n_msgs && capacity_bytes) {
         const unsigned blocks = (unsigned)pack_blocks(capacity_bytes);
         hipLaunchKernelGGL(k_frames_copy, dim3(blocks), dim3(kPackLanes), 0, s, in, d_frame_offsets, d_frames,

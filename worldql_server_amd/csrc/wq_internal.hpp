@@ -51,6 +51,26 @@ struct DevBuf {
     }
 };
 
+// A device buffer that is all zero between the calls that use it. The select of the send budgets
+// (wq_budget.hip) needs every bin of its histograms zero when a call starts. Every pick pass zeroes
+// the bins it read, so a call that launched all its passes leaves them zero: `clean` is the number of
+// bytes known to be zero. It is 0 for a new allocation (decided from the capacity, not the address:
+// a freed block's address can come back) and between begin() and end(), while a call's passes are
+// being launched, so a call that failed between a histogram pass and its pick makes the next one
+// clear the buffer.
+struct ZeroedBuf {
+    DevBuf b;
+    size_t clean = 0;
+    // Room for `need` bytes, all zero once the stream reaches this point (defined below the handle).
+    int prepare(wq_router* h, size_t need, hipStream_t stream);
+    void begin() { clean = 0; }
+    void end() { clean = b.bytes; }
+    void release() {
+        b.release();
+        clean = 0;
+    }
+};
+
 // The live subscription set, sorted by (hash, world, key, peer): one entry per
 // (world, cube, peer) triple. Everything the route kernel reads is derived from it.
 struct State {
@@ -244,23 +264,26 @@ struct wq_router {
     // call zeroes the next call's) followed by the host form's counters
     wq::DevBuf diff_len, diff_pre, diff_cnt, diff_base, diff_flags, diff_err;
     uint64_t diff_calls = 0;
-    // send budgets (wq_budget.hip): per peer the clamped lengths / kept counts, their saturating prefix
-    // and the ordinal space; per ordinal the key, row and class; per slot of kBudShort ordinals the
-    // select's state and histogram; per granule of 64 the tie and keep flag words, counts and prefixes;
-    // {rows_cut, error}
-    wq::DevBuf bud_len, bud_sum, bud_pre, bud_key, bud_row, bud_cls, bud_sel, bud_hist, bud_words, bud_cnt, bud_base,
-        bud_ctrl;
-    size_t bud_hist_clean = 0;  // bytes of bud_hist known to be zero (0: clear before the next select)
+    // the send side's ordinal space (send_rows.hpp rows_alloc / rows_view), shared by the budgets, the
+    // fair share and the send buffers: per peer the clamped lengths (then the kept or chosen counts),
+    // their saturating prefix and the prefix clamped to n_in
+    wq::DevBuf bud_len, bud_sum, bud_pre;
+    // send budgets (wq_budget.hip): per ordinal the key, row and class; per slot of kBudShort ordinals
+    // the select's state and u32 histogram; per granule of 64 the tie and keep flag words, counts and
+    // prefixes; {rows_cut, error}
+    wq::DevBuf bud_key, bud_row, bud_cls, bud_sel, bud_words, bud_cnt, bud_base, bud_ctrl;
+    wq::ZeroedBuf bud_hist;
     // byte budgets (wq_budget.hip): they run on the buffers above and add, per ordinal, the size and
-    // one u64 scan entry, and per slot the weighted select's state and u64 histogram, zero between
-    // calls under a clean-byte count of its own, so the two calls alternate on one handle
-    wq::DevBuf byt_size, byt_scan, byt_sel, byt_hist;
-    size_t byt_hist_clean = 0;
-    // fair share (wq_rotate.hip): it runs on the buffers above (the full CSR's rows, the per-ordinal
-    // row and size, the u64 scan, the flag words, ctrl) and adds the kept CSR's rows and, per peer, the
-    // folded scan terms of its row (RotRow), and the slots the counters' adds are spread over
+    // one u64 scan entry, and per slot the weighted select's state and u64 histogram: a zeroed buffer
+    // of its own, so the two calls alternate on one handle
+    wq::DevBuf byt_size, byt_scan, byt_sel;
+    wq::ZeroedBuf byt_hist;
+    // fair share (wq_rotate.hip): it runs on the buffers above (the full CSR's ordinal space, the
+    // per-ordinal row and size, the u64 scan, the flag words, ctrl) and adds the kept CSR's ordinal
+    // space and, per peer, the folded scan terms of its row (RotRow), and the slots the counters' adds
+    // are spread over
     wq::DevBuf rot_len, rot_sum, rot_pre, rot_rows, rot_part;
-    // send buffers (wq_pack.hip): the rows run on bud_len / bud_sum / bud_pre above; per ordinal the
+    // send buffers (wq_pack.hip): the rows run on the shared ordinal space above; per ordinal the
     // frame's size, where it starts and one u64 scan entry; {unused, error}
     wq::DevBuf pack_size, pack_src, pack_scan, pack_ctrl;
     // frame builder (wq_frames.hip): per message the frame's size; {unused, error}; the world table
@@ -454,3 +477,14 @@ void multi_release(wq_router* h);
         hipError_t e_ = (buf).ensure(bytes);                                        \
         if (e_ != hipSuccess) return wq::set_error((h), WQ_E_OOM, "hipMalloc " #buf, e_); \
     } while (0)
+
+inline int wq::ZeroedBuf::prepare(wq_router* h, size_t need, hipStream_t stream) {
+    const size_t cap = b.bytes;
+    WQ_ALLOC(h, b, need);
+    if (b.bytes != cap) clean = 0;
+    if (clean < b.bytes) {
+        WQ_HIP(h, hipMemsetAsync(b.p, 0, b.bytes, stream));
+        clean = b.bytes;
+    }
+    return WQ_OK;
+}

@@ -7,7 +7,7 @@
 // (transport/peer_map.rs:22-40) clones the bytes and sends once per recipient on the host.
 //
 //   rows   one lane per peer: the clamped length; the saturating scan and the clamp to n_in give the
-//          ordinal space (budget_ops.hpp, as the budgets)
+//          ordinal space (send_rows.hpp, as the budgets)
 //   size   one lane per ordinal: its row (a search over the prefix), its message, its frame under the
 //          validity rules (pack_ops.hpp): the frame's size and where it starts
 //   scan   one u64 exclusive scan of the record sizes over the ordinals: E
@@ -27,7 +27,7 @@
 // frames are windows of one tile. Placement comes from the scans alone; the only atomics are ORs
 // into the error word, so the output is the same bytes every time.
 #include "pack_ops.hpp"
-#include "table_prims.hpp"
+#include "send_rows.hpp"
 
 namespace wq {
 
@@ -64,29 +64,11 @@ struct PackTerm {
     }
 };
 
-__global__ __launch_bounds__(kBlock) void k_pack_len(PackIn in, PackWs ws) {
-    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p > in.n_peers) return;
-    bool ok = true;
-    ws.len[p] = p < in.n_peers ? bud_len(in.off, (uint32_t)p, in.n_in, &ok) : 0u;
-    if (!ok) atomicOr(&ws.ctrl[1], kBudErrRows);
-}
-
-__global__ __launch_bounds__(kBlock) void k_pack_pre(PackIn in, PackWs ws) {
-    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p > in.n_peers) return;
-    const uint32_t a = ws.sum[p] < in.n_in ? ws.sum[p] : in.n_in;
-    ws.pre[p] = a;
-    if (p == in.n_peers) return;
-    const uint32_t b = ws.sum[p + 1] < in.n_in ? ws.sum[p + 1] : in.n_in;
-    if (b - a != ws.len[p]) atomicOr(&ws.ctrl[1], kBudErrRows);  // overlapping rows: cut at n_in ordinals
-}
-
 __global__ __launch_bounds__(kBlock) void k_pack_size(PackIn in, PackWs ws) {
     const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (q >= ws.pre[in.n_peers]) return;
     const uint32_t p = bud_row_of(ws.pre, in.n_peers, (uint32_t)q);
-    const uint32_t j = bud_row_start(in.off, p, in.n_in) + ((uint32_t)q - ws.pre[p]);
+    const uint32_t j = rows_elem(in.off, ws.pre, in.n_in, p, (uint32_t)q);
     uint32_t err = 0;
     uint64_t src;
     ws.size[q] = pack_frame(in.fo, in.n_msgs, in.n_frame_bytes, in.msgs[j], &src, &err);
@@ -166,25 +148,6 @@ __global__ void k_pack_counters(PackWs ws, uint32_t n_peers, uint64_t capacity, 
     *counters = c;
 }
 
-int pack_scan_sat(wq_router* h, const uint32_t* in, uint32_t* out, size_t n) {
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
-    return WQ_OK;
-}
-
-// Exclusive u64 scan of the n terms f(0 .. n).
-int pack_scan_bytes(wq_router* h, const PackTerm& f, uint64_t* out, size_t n) {
-    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), f);
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                      h->stream));
-    return WQ_OK;
-}
-
 }  // namespace
 
 void pack_release(wq_router* h) {
@@ -192,17 +155,15 @@ void pack_release(wq_router* h) {
 }
 
 // The call on device arrays (the handle's device is current; arguments validated, n_in <= 2^32 - 1).
-// The rows' three buffers are the budgets': the calls are ordered on the handle's stream and nothing
-// in them outlives a call. Everything else is this path's own.
+// The ordinal space's three buffers are the budgets' (send_rows.hpp rows_alloc): the calls are ordered
+// on the handle's stream and nothing in them outlives a call. Everything else is this path's own.
 int launch_peer_pack(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers, size_t n_in,
                      const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_msgs, size_t n_frame_bytes,
                      uint32_t flags, uint8_t* d_out, size_t capacity_bytes, uint64_t* d_out_peer_bytes,
                      uint64_t* d_out_elem_bytes, wq_pack_counters* d_counters) {
     hipStream_t s = h->stream;
     const size_t rows = (size_t)n_peers + 1;
-    WQ_ALLOC(h, h->bud_len, rows * 4);
-    WQ_ALLOC(h, h->bud_sum, rows * 4);
-    WQ_ALLOC(h, h->bud_pre, rows * 4);
+    if (int rc = rows_alloc(h, rows)) return rc;
     WQ_ALLOC(h, h->pack_size, n_in * 4);
     WQ_ALLOC(h, h->pack_src, n_in * 8);
     WQ_ALLOC(h, h->pack_scan, (n_in + 1) * 8);
@@ -211,22 +172,22 @@ int launch_peer_pack(wq_router* h, const uint32_t* d_peer_offsets, const uint32_
 
     const PackIn in{d_peer_offsets, d_msgs,  d_frames,       d_frame_offsets,         (uint64_t)n_msgs, (uint64_t)n_frame_bytes,
                     n_peers,        (uint32_t)n_in, pack_prefix_bytes(flags)};
-    const PackWs ws{h->bud_len.as<uint32_t>(),   h->bud_sum.as<uint32_t>(),  h->bud_pre.as<uint32_t>(),
-                    h->pack_size.as<uint32_t>(), h->pack_src.as<uint64_t>(), h->pack_scan.as<uint64_t>(),
-                    h->pack_ctrl.as<uint32_t>()};
+    const RowSpace r = rows_view(h, d_peer_offsets, n_peers, n_in);
+    const PackWs ws{r.len, r.sum, r.pre, h->pack_size.as<uint32_t>(), h->pack_src.as<uint64_t>(),
+                    h->pack_scan.as<uint64_t>(), h->pack_ctrl.as<uint32_t>()};
 
     const dim3 blk(kBlock);
     const dim3 grid_r(grid_for(rows));
-    hipLaunchKernelGGL(k_pack_len, grid_r, blk, 0, s, in, ws);
+    hipLaunchKernelGGL(k_rows_len, grid_r, blk, 0, s, r, ws.ctrl + 1, kBudErrRows);
     WQ_HIP(h, hipGetLastError());
-    if (int rc = pack_scan_sat(h, ws.len, ws.sum, rows)) return rc;
-    hipLaunchKernelGGL(k_pack_pre, grid_r, blk, 0, s, in, ws);
+    if (int rc = scan_sat(h, ws.len, ws.sum, rows)) return rc;
+    hipLaunchKernelGGL(k_rows_pre, grid_r, blk, 0, s, r, ws.ctrl + 1, kBudErrRows);
     WQ_HIP(h, hipGetLastError());
     if (n_in) {
         hipLaunchKernelGGL(k_pack_size, dim3(grid_for(n_in)), blk, 0, s, in, ws);
         WQ_HIP(h, hipGetLastError());
     }
-    if (int rc = pack_scan_bytes(h, PackTerm{ws.size, ws.pre + n_peers, in.pre}, ws.E, n_in + 1)) return rc;
+    if (int rc = scan_terms(h, PackTerm{ws.size, ws.pre + n_peers, in.pre}, ws.E, n_in + 1)) return rc;
     hipLaunchKernelGGL(k_pack_peer_bytes, grid_r, blk, 0, s, ws, n_peers, d_out_peer_bytes);
     WQ_HIP(h, hipGetLastError());
     if (n_in && d_out_elem_bytes) {

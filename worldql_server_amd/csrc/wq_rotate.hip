@@ -7,7 +7,7 @@
 // The state is one u32 per peer.
 //
 //   rows    one lane per peer: the clamped lengths of the full and the kept row; two saturating scans
-//           give both ordinal spaces (budget_ops.hpp); a second lane per peer: P, the upper bound of
+//           give both ordinal spaces (send_rows.hpp); a second lane per peer: P, the upper bound of
 //           the cursor in the full row (a binary search)
 //   cut     a wave per granule of 64 ordinals: the element's row (a search over the prefix), its
 //           occurrence index, its value's lower and upper bound in the kept row, the ballot of "cut";
@@ -25,7 +25,7 @@
 // of adds to one address cost more than the rest of the call. The cursors are read in
 // `rows` and written by `emit`, the call's last kernel.
 #include "rotate_ops.hpp"
-#include "table_prims.hpp"
+#include "send_rows.hpp"
 
 namespace wq {
 
@@ -63,37 +63,29 @@ struct RotWs {
     RotPart* part;    // [kRotParts] partial sums of bytes_chosen, rows_rotated, rows_behind; zero at the start
 };
 
-struct RotTerm {
-    const uint32_t* size;
-    const uint64_t* words;
-    const uint32_t* T;
-    __host__ __device__ __forceinline__ uint64_t operator()(uint64_t q) const {
-        return bud_byte_term(size, words, *T, q);
-    }
-};
+// The ordinal spaces of the full and of the kept CSR.
+__device__ __forceinline__ RowSpace rot_full(const RotIn& in, const RotWs& ws) {
+    return RowSpace{in.off, in.n_peers, in.n_in, ws.len, ws.sum, ws.pre};
+}
+__device__ __forceinline__ RowSpace rot_kept(const RotIn& in, const RotWs& ws) {
+    return RowSpace{in.koff, in.n_peers, in.n_kin, ws.klen, ws.ksum, ws.kpre};
+}
 
 __global__ __launch_bounds__(kBlock) void k_rot_len(RotIn in, RotWs ws) {
     const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p > in.n_peers) return;
-    bool ok = true, kok = true;
-    ws.len[p] = p < in.n_peers ? bud_len(in.off, (uint32_t)p, in.n_in, &ok) : 0u;
-    ws.klen[p] = p < in.n_peers ? bud_len(in.koff, (uint32_t)p, in.n_kin, &kok) : 0u;
-    if (!ok || !kok) atomicOr(&ws.ctrl[1], kRotErrRows);
+    rows_len_step(rot_full(in, ws), p, &ws.ctrl[1], kRotErrRows);
+    rows_len_step(rot_kept(in, ws), p, &ws.ctrl[1], kRotErrRows);
 }
 
 __global__ __launch_bounds__(kBlock) void k_rot_pre(RotIn in, RotWs ws, const uint32_t* __restrict__ cursor) {
     const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p > in.n_peers) return;
-    const uint32_t a = ws.sum[p] < in.n_in ? ws.sum[p] : in.n_in;
-    const uint32_t ka = ws.ksum[p] < in.n_kin ? ws.ksum[p] : in.n_kin;
-    ws.pre[p] = a;
-    ws.kpre[p] = ka;
+    uint32_t len, klen;
+    const uint32_t a = rows_pre_step(rot_full(in, ws), p, &ws.ctrl[1], kRotErrRows, &len);
+    rows_pre_step(rot_kept(in, ws), p, &ws.ctrl[1], kRotErrRows, &klen);
     if (p == in.n_peers) return;
-    const uint32_t b = ws.sum[p + 1] < in.n_in ? ws.sum[p + 1] : in.n_in;
-    const uint32_t kb = ws.ksum[p + 1] < in.n_kin ? ws.ksum[p + 1] : in.n_kin;
-    if (b - a != ws.len[p] || kb - ka != ws.klen[p])
-        atomicOr(&ws.ctrl[1], kRotErrRows);  // overlapping rows: cut at the array's element count
-    ws.rrow[p].P = a + rot_upper(in.msgs + bud_row_start(in.off, (uint32_t)p, in.n_in), b - a, cursor[p]);
+    ws.rrow[p].P = a + rot_upper(in.msgs + bud_row_start(in.off, (uint32_t)p, in.n_in), len, cursor[p]);
 }
 
 __global__ __launch_bounds__(kBlock) void k_rot_cut(RotIn in, RotWs ws, uint32_t nG) {
@@ -114,11 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_rot_cut(RotIn in, RotWs ws, uint32_t
             if (m >= in.n_msgs) atomicOr(&ws.ctrl[1], kRotErrMsg);
         }
     }
-    const uint64_t word = __ballot(cut);
-    if ((threadIdx.x & 63u) == 0) {
-        ws.words[g] = word;
-        ws.cnt[g] = (uint32_t)__popcll(word);
-    }
+    store_flags(ws.words, ws.cnt, g, cut);
 }
 
 __global__ __launch_bounds__(kBlock) void k_rot_rowq(RotIn in, RotWs ws) {
@@ -140,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void k_rot_keep(RotIn in, RotWs ws, uint32_
     unsigned long long mine = 0;
     if (g < nG && x < ws.pre[in.n_peers]) {
         f = true;
-        if ((ws.words[g] >> lane) & 1ull) {
+        if (flag_at(ws.words, x)) {
             const uint32_t p = ws.row[x];
             const RotRow r = ws.rrow[p];
             const uint32_t rank = rot_rank(r, (uint32_t)x, bud_before(ws.base, ws.words, (uint32_t)x));
@@ -151,11 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_rot_keep(RotIn in, RotWs ws, uint32_
             if (f) mine = sz;
         }
     }
-    const uint64_t word = __ballot(f);
-    if (g < nG && lane == 0) {
-        ws.words[(uint64_t)nG + g] = word;
-        ws.cnt[(uint64_t)nG + g] = (uint32_t)__popcll(word);
-    }
+    if (g < nG) store_flags(ws.words, ws.cnt, (uint64_t)nG + g, f);  // wave-uniform
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d);
     if (lane == 0) wave_bytes[wave] = mine;
@@ -232,34 +216,15 @@ __global__ __launch_bounds__(kBlock) void k_rot_emit(RotIn in, RotWs ws, uint32_
     const uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (x >= ws.pre[in.n_peers]) return;
     const uint64_t* keep = ws.words + nG;
-    if (!((keep[x >> 6] >> (x & 63u)) & 1ull)) return;
+    if (!flag_at(keep, x)) return;
     const uint32_t p = ws.row[x];
-    const uint32_t m = in.msgs[bud_row_start(in.off, p, in.n_in) + ((uint32_t)x - ws.pre[p])];
+    const uint32_t m = in.msgs[rows_elem(in.off, ws.pre, in.n_in, p, (uint32_t)x)];
     const uint32_t pos = bud_before(ws.base + nG, keep, (uint32_t)x);
     if (pos < in.n_in) out[pos] = m;
-    if ((ws.words[x >> 6] >> (x & 63u)) & 1ull) {  // chosen: the one of the largest rank moves the cursor
+    if (flag_at(ws.words, x)) {  // chosen: the one of the largest rank moves the cursor
         const uint32_t rank = rot_rank(ws.rrow[p], (uint32_t)x, bud_before(ws.base, ws.words, (uint32_t)x));
         if (rank + 1 == ws.len[p]) cursor[p] = m;
     }
-}
-
-int rot_scan_sat(wq_router* h, const uint32_t* in, uint32_t* out, size_t n) {
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
-    return WQ_OK;
-}
-
-// Exclusive u64 scan of the n terms f(0 .. n).
-int rot_scan_bytes(wq_router* h, const RotTerm& f, uint64_t* out, size_t n) {
-    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), f);
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                      h->stream));
-    return WQ_OK;
 }
 
 }  // namespace
@@ -269,9 +234,10 @@ void rotate_release(wq_router* h) {
 }
 
 // The call on device arrays (the handle's device is current; arguments validated). The full CSR's
-// rows, the per-ordinal row and size, the u64 scan, the flag words and ctrl are the budgets' buffers:
-// the calls are ordered on the handle's stream and nothing in them outlives a call. The kept CSR's
-// rows, RotRow and the counters' slots are this path's own.
+// ordinal space (send_rows.hpp rows_alloc), the per-ordinal row and size, the u64 scan, the flag
+// words and ctrl are the budgets' buffers: the calls are ordered on the handle's stream and nothing
+// in them outlives a call. The kept CSR's ordinal space, RotRow and the counters' slots are this
+// path's own.
 int launch_peer_rotate(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,
                        size_t n_in, const uint32_t* d_kept_offsets, const uint32_t* d_kept_msgs, size_t n_kept_in,
                        const uint32_t* d_msg_size, size_t n_msgs, uint32_t r, const uint32_t* d_extra, uint64_t v,
@@ -280,9 +246,7 @@ int launch_peer_rotate(wq_router* h, const uint32_t* d_peer_offsets, const uint3
     hipStream_t s = h->stream;
     const size_t rows = (size_t)n_peers + 1;
     const uint32_t nG = (uint32_t)(n_in / 64 + 1);
-    WQ_ALLOC(h, h->bud_len, rows * 4);
-    WQ_ALLOC(h, h->bud_sum, rows * 4);
-    WQ_ALLOC(h, h->bud_pre, rows * 4);
+    if (int rc = rows_alloc(h, rows)) return rc;
     WQ_ALLOC(h, h->rot_len, rows * 4);
     WQ_ALLOC(h, h->rot_sum, rows * 4);
     WQ_ALLOC(h, h->rot_pre, rows * 4);
@@ -314,15 +278,15 @@ int launch_peer_rotate(wq_router* h, const uint32_t* d_peer_offsets, const uint3
     const uint32_t* d_T = ws.pre + n_peers;
     hipLaunchKernelGGL(k_rot_len, grid_r, blk, 0, s, in, ws);
     WQ_HIP(h, hipGetLastError());
-    if (int rc = rot_scan_sat(h, ws.len, ws.sum, rows)) return rc;
-    if (int rc = rot_scan_sat(h, ws.klen, ws.ksum, rows)) return rc;
+    if (int rc = scan_sat(h, ws.len, ws.sum, rows)) return rc;
+    if (int rc = scan_sat(h, ws.klen, ws.ksum, rows)) return rc;
     hipLaunchKernelGGL(k_rot_pre, grid_r, blk, 0, s, in, ws, (const uint32_t*)d_cursor);
     WQ_HIP(h, hipGetLastError());
     hipLaunchKernelGGL(k_rot_cut, grid_g, blk, 0, s, in, ws, nG);
     WQ_HIP(h, hipGetLastError());
     if (int rc = scan_u32(h, ws.cnt, ws.base, nG, false)) return rc;
     if (d_msg_size)
-        if (int rc = rot_scan_bytes(h, RotTerm{ws.size, ws.words, d_T}, ws.scan, n_in + 1)) return rc;
+        if (int rc = scan_terms(h, SizeTerm{ws.size, ws.words, d_T}, ws.scan, n_in + 1)) return rc;
     if (n_peers) {
         hipLaunchKernelGGL(k_rot_rowq, dim3(grid_for(n_peers)), blk, 0, s, in, ws);
         WQ_HIP(h, hipGetLastError());
@@ -332,7 +296,7 @@ int launch_peer_rotate(wq_router* h, const uint32_t* d_peer_offsets, const uint3
     if (int rc = scan_u32(h, ws.cnt + nG, ws.base + nG, nG, false)) return rc;
     const uint64_t* kept_scan = nullptr;
     if (d_msg_size && (d_out_bytes || d_counters)) {
-        if (int rc = rot_scan_bytes(h, RotTerm{ws.size, ws.words + nG, d_T}, ws.scan, n_in + 1)) return rc;
+        if (int rc = scan_terms(h, SizeTerm{ws.size, ws.words + nG, d_T}, ws.scan, n_in + 1)) return rc;
         kept_scan = ws.scan;
     }
     hipLaunchKernelGGL(k_rot_offsets, grid_r, blk, 0, s, in, ws, nG, d_out_offsets, d_out_bytes);
