@@ -1462,6 +1462,170 @@ int wq_region_quantize(const double* coords, size_t n, uint16_t size, int64_t* o
 /* clamp_table_size (world_region.rs:112-129) on the host. */
 int wq_table_quantize(const int64_t* region, size_t n, uint32_t table_size, int64_t* out);
 
+/* ---- record dispatch: a tick's record frames to store ops and queries on the device ----
+ * wq_ingest_dispatch_device lists the RecordCreate / RecordRead / RecordDelete frames of a tick
+ * (WQ_CLS_DB, the database segment of side_src) and leaves the record path to the caller. The reference
+ * handles them one message at a time (processing/record_create.rs:15-18, record_read.rs:18-41,
+ * record_delete.rs:15-18: "@global" is ignored; database/client.rs:86-111 and :365-379: a record without
+ * a position or with a world name the sanitizer refuses is dropped; utils/time.rs:6-16: the `after` of a
+ * read) and records.RecordProcessor.process restates that as a Python loop over every record. Here one
+ * call walks the listed frames' records where the frames lie and writes the arrays wq_records_apply_device
+ * and wq_records_read_device take, with the table of runs that says in which order to issue them. Nothing
+ * is read back until the counters and the run table. The host definition is ingest.records_dispatch_np.
+ *
+ * Input (wq_recdisp_in; device pointers unless stated)
+ *   - frames / frame_offsets[n_frames + 1] / n_frame_bytes: the tick's raw frames as the decoder took them;
+ *     msg / world / flags: the decoder's outputs, [n_frames] each.
+ *   - db_src[n_db]: ascending frame indices; NULL means frames 0 .. n_db - 1.
+ *   - now_us: the ts_us of every op. free_handles[n_free] (nullable with n_free 0) / handle_next: the k-th
+ *     accepted create of the call gets free_handles[k] for k < n_free, else handle_next + (k - n_free); the
+ *     caller updates its allocator from n_creates.
+ *   - max_records: the caller's bound on the records the listed frames hold, < 2^32 - 64. Scratch is sized
+ *     from it, never from a value read back. Every record owns a 4-byte slot of its frame's records vector,
+ *     so n_frame_bytes / 4 always suffices. Records past the bound are not examined: overflow bit 3.
+ * Frame classes (out->cls[j] for listed entry j, frame f = db_src[j])
+ *   - WQ_RCLS_SKIP           flag bit 0 clear, flag bit 4 set (the message's world is "@global"), or an
+ *                            instruction other than 8, 9, 11. Also a listed index >= n_frames.
+ *   - WQ_RCLS_APPLY          instruction 8 (create) or 11 (delete). The message's own world plays no further
+ *                            part; each record carries its own.
+ *   - WQ_RCLS_READ           instruction 9 with a position (flag bit 1), a parameter that is absent (flag bit
+ *                            2 clear) or parses, a world name the sanitizer accepts and a resolved world (flag
+ *                            bit 5 and world < WQ_WORLD_GLOBAL). One query row.
+ *   - WQ_RCLS_READ_DROPPED   instruction 9 without a position, or with a parameter that does not parse, or
+ *                            with a world name the sanitizer refuses (dec_sanitize over msg.world_off / len
+ *                            inside the frame tells "refused" from "unknown"). Checked in that order.
+ *   - WQ_RCLS_READ_DEFERRED  instruction 9 that passes those checks but whose world did not resolve: the
+ *                            host interns the name. Listed in defer with record WQ_RDEFER_READ.
+ *   - Parameter: u64::from_str — an optional single '+', then one or more ASCII digits and nothing else,
+ *     leading zeros allowed, the value below 2^64 — then chrono's range, ms / 1000 <= 8,210,298,412,799.
+ *     q_after = ms * 1000; "no after" is INT64_MIN. The lane stops at the first byte that is no digit and
+ *     once the significant digits exceed 20; a run of leading zeros is the only long walk, bounded by the
+ *     frame. (records.parse_epoch_millis goes through Python's int(), which refuses very long digit
+ *     strings; this definition parses digit by digit and follows time.rs.)
+ * Records of an APPLY frame, in (frame, record index) order; the count is the vector's in the frame, never
+ * msg.n_records
+ *   - dropped and counted by reason: no position; a world name the sanitizer refuses ("@global" is refused
+ *     with IsGlobalWorld); rec_pack_position fails under the open store's configuration (a NaN, a region
+ *     index outside [-2^23, 2^23)).
+ *   - deferred: the sanitized name is not in the handle's world table (wq_frames_set_worlds). Listed in
+ *     defer as (frame, record index); the host interns the name and applies the record after the tick.
+ *   - accepted: one wq_rec_op { kind, world, the position's bits as they lie, uuid_hi / uuid_lo (the
+ *     big-endian halves of the uuid re-parsed from its text), ts_us = now_us, handle (create: from the
+ *     allocator; delete: 0), reserved 0 }: byte for byte the rows RecordProcessor.process assembles.
+ *     op_ref beside it holds the frame and record index, where the record's data and flex lie inside the
+ *     frame and whether they are present (bits 0 and 1), so the caller copies the payload into its slab
+ *     under the op's handle before the frame buffer is reused.
+ * Runs: RecordProcessor.process's non-empty apply and read calls, in its order, each with the same rows
+ *   - process keeps one batch of ops and one of reads. A barrier is a listed frame of class APPLY (kind
+ *     apply) or READ / READ_DROPPED / READ_DEFERRED (kind read): it flushes the other kind's batch, whether or
+ *     not it yields a row itself. An effective frame has at least one accepted op or is a READ: it joins its
+ *     kind's batch, and starts a run when that batch is empty — no effective frame of its kind has come since
+ *     the last barrier of the other kind.
+ *   - Two consecutive runs may have the same kind (reads, a create frame without an accepted record, reads),
+ *     and a barrier that yields nothing still ends the other kind's run (creates, a dropped read, a read: an
+ *     apply run and a read run). The split of a read batch is observable, see "two queries of one read
+ *     call" under the record store above.
+ *   - runs[r] = { kind (WQ_RRUN_APPLY / WQ_RRUN_READ), the run's first frame, where its rows begin in ops
+ *     and in q_* }; runs[n_runs] closes the table with WQ_RRUN_END, first_frame = n_frames and the totals.
+ *     Rows are stable, so a run's rows are contiguous.
+ *   - With no deferred entry the outcome equals RecordProcessor.process's. With deferred entries it is
+ *     exact for every frame before first_deferred.
+ * Output (wq_recdisp_out: device pointers, each nullable, at natural alignment)
+ *   - cls[n_db]; q_src / q_world / q_pos (3 f64) / q_after (i64), [n_db] each: q_world, q_pos, q_after are
+ *     the arrays wq_records_read_device takes; ops / op_ref[ops_capacity]; defer[defer_capacity]: (frame,
+ *     record) ascending; runs[runs_capacity].
+ *   - Rows below a capacity are exact; the counters and the closing run (when it fits) are always complete:
+ *     overflow bit 0 ops, 1 defer, 2 runs, 3 max_records. A NULL array with capacity 0 makes a sizing call.
+ *     Nothing is written outside [0, count) of each array; the inputs are never written.
+ * Hostile input (never a fault): the arrays are the caller's and may disagree with the frames.
+ *   - No byte is read outside frames[0 .. n_frame_bytes), frame_offsets[0 .. n_frames], db_src[0 .. n_db)
+ *     and the n_frames-sized arrays; every access to a frame goes through the decoder's bounded reader.
+ *   - error bit 0: a walk failed — frame offsets the decoder would refuse, a records vector, record table,
+ *     uuid, parameter or world range that does not lie in the frame. Such a frame or record yields nothing
+ *     (an APPLY frame keeps its class with no records, a read is READ_DROPPED) and a record counts in
+ *     n_drop_walk. error bit 1: a db_src entry >= n_frames (SKIP) or not above its predecessor (processed
+ *     in list order all the same).
+ *   - Every loop is bounded by the frame's size or by max_records; nothing spins or waits on another lane.
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. A frame pass (one lane per listed frame:
+ *     class, parameter, the records vector), a scan of the record counts, a record pass (element-parallel
+ *     over granules of 64 records on a grid-stride loop: every lane finds its frame by search and
+ *     evaluates one record; wave ballots give the granule's flag words), scans of the granules' counts, the
+ *     scan over the listed frames that carries rows and runs (a frame's own sum is computed from the granules'
+ *     prefixes as the scan reads it), and a stable emit that walks the accepted records once more. No lane, wave or block owns a frame's records.
+ *     Deterministic byte for byte: the only atomics are integer adds and ORs into the counters.
+ *   - Scratch lives in the handle, grow-only: 57 bytes per listed frame and 40 bytes per 64 records of
+ *     max_records. A steady-state call does no hipMalloc, and the call alternates freely with decode,
+ *     dispatch, route, records apply / read, builder and pack on one handle.
+ *   - WQ_E_INVALID, with nothing launched, for a null handle, in or out; a null required array with a
+ *     non-zero size (frames, frame_offsets, msg, world, flags); no open record store (a multi-GPU handle has none);
+ *     n_db >= 2^32 - 1 or n_frames >= 2^32 - 1; max_records >= 2^32 - 64; n_free > 0 without free_handles;
+ *     an array given with capacity 0, or a capacity without its array (ops and op_ref share ops_capacity). */
+#define WQ_RCLS_SKIP 0
+#define WQ_RCLS_APPLY 1
+#define WQ_RCLS_READ 2
+#define WQ_RCLS_READ_DROPPED 3
+#define WQ_RCLS_READ_DEFERRED 4
+#define WQ_RCLS_COUNT 5
+
+#define WQ_RRUN_END 0
+#define WQ_RRUN_APPLY 1
+#define WQ_RRUN_READ 2
+
+#define WQ_RDEFER_READ 0xFFFFFFFFu   /* wq_recdisp_defer.record of a deferred read */
+
+struct wq_decoded_msg;
+typedef struct wq_recdisp_in {
+    const uint8_t*  frames;          /* [n_frame_bytes] */
+    const uint64_t* frame_offsets;   /* [n_frames + 1] */
+    uint64_t        n_frames, n_frame_bytes;
+    const struct wq_decoded_msg* msg; /* [n_frames] */
+    const uint32_t* world;           /* [n_frames] */
+    const uint8_t*  flags;           /* [n_frames] */
+    const uint32_t* db_src;          /* [n_db] nullable: frames 0 .. n_db - 1 */
+    uint64_t        n_db;
+    int64_t         now_us;
+    const uint32_t* free_handles;    /* [n_free] nullable with n_free 0 */
+    uint32_t        n_free, handle_next;
+    uint64_t        max_records;
+} wq_recdisp_in;             /* 104 bytes */
+
+typedef struct wq_rec_op_ref {
+    uint32_t frame, record;          /* the frame index and the record's index in its vector */
+    uint32_t data_off, data_len, flex_off, flex_len;  /* inside the frame; 0, 0 when absent */
+    uint32_t bits;                   /* bit 0: data present, bit 1: flex present */
+    uint32_t pad_;
+} wq_rec_op_ref;             /* 32 bytes */
+
+typedef struct wq_recdisp_defer { uint32_t frame, record; } wq_recdisp_defer;                      /* 8 bytes */
+typedef struct wq_recdisp_run { uint32_t kind, first_frame, op_begin, q_begin; } wq_recdisp_run;   /* 16 bytes */
+
+typedef struct wq_recdisp_out {      /* device pointers, each nullable */
+    uint8_t*  cls;                   /* [n_db] WQ_RCLS_* */
+    wq_rec_op* ops; wq_rec_op_ref* op_ref;                               /* [ops_capacity] */
+    uint32_t* q_src; uint32_t* q_world; double* q_pos; int64_t* q_after; /* [n_db] query rows */
+    wq_recdisp_defer* defer;         /* [defer_capacity] */
+    wq_recdisp_run* runs;            /* [runs_capacity] runs[0 .. min(n_runs + 1, capacity)) */
+    uint32_t ops_capacity, defer_capacity, runs_capacity, pad_;
+} wq_recdisp_out;            /* 88 bytes */
+
+typedef struct wq_recdisp_counters {
+    uint64_t n_db;
+    uint64_t n_skip, n_apply, n_read, n_read_dropped, n_read_deferred;   /* listed frames per WQ_RCLS_* */
+    uint64_t n_records_total;        /* records the APPLY frames hold */
+    uint64_t n_records;              /* of them examined: min(n_records_total, max_records) */
+    uint64_t n_creates, n_deletes;   /* accepted */
+    uint64_t n_drop_walk, n_drop_no_position, n_drop_world, n_drop_unpackable;  /* dropped, by reason */
+    uint64_t n_deferred_records;     /* deferred reads: n_read_deferred */
+    uint64_t n_runs;
+    uint64_t first_deferred;         /* the frame index of the first deferred entry; n_frames when there is none */
+    uint64_t overflow;               /* bits 0 - 3 above */
+    uint64_t error;                  /* bits 0 and 1 above */
+} wq_recdisp_counters;       /* 152 bytes */
+
+int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,
+                               wq_recdisp_counters* d_counters /* nullable */);
+
 /* ---- health of asynchronous ticks ----
  * OR of wq_route_counters.error (error_bits) and of .overflow over every route / global call since
  * the previous wq_route_health on this handle; reading clears them (synchronises the stream). A

@@ -161,6 +161,49 @@ assert ctypes.sizeof(DispatchIn) == 64 and ctypes.sizeof(DispatchOut) == 120
 assert DISPATCH_RUN_DTYPE.itemsize == 20 and DISPATCH_COUNTERS_DTYPE.itemsize == 168
 
 
+# ---- record dispatch (wq_records_dispatch_device) ----
+# WQ_RCLS_*: the class of a listed frame, in the order of wq_recdisp_counters' per-class counts
+RCLS_SKIP, RCLS_APPLY, RCLS_READ, RCLS_READ_DROPPED, RCLS_READ_DEFERRED = range(5)
+RCLS_NAMES = ("skip", "apply", "read", "read_dropped", "read_deferred")
+RRUN_END, RRUN_APPLY, RRUN_READ = 0, 1, 2      # WQ_RRUN_*: wq_recdisp_run.kind
+RDEFER_READ = 0xFFFFFFFF                       # WQ_RDEFER_READ: wq_recdisp_defer.record of a deferred read
+RECDISP_ERROR_WALK, RECDISP_ERROR_LIST = 1, 2  # wq_recdisp_counters.error bits 0 and 1
+RECDISP_OVERFLOW_OPS, RECDISP_OVERFLOW_DEFER, RECDISP_OVERFLOW_RUNS, RECDISP_OVERFLOW_RECORDS = 1, 2, 4, 8
+RECDISP_MAX_RECORDS = 0xFFFFFFC0               # max_records stays below
+# struct wq_rec_op_ref: 32 bytes; wq_recdisp_defer: 8; wq_recdisp_run: 16
+REC_OP_REF_DTYPE = np.dtype([(k, np.uint32) for k in ("frame", "record", "data_off", "data_len", "flex_off", "flex_len",
+                                                      "bits", "pad_")])
+RECDISP_DEFER_DTYPE = np.dtype([("frame", np.uint32), ("record", np.uint32)])
+RECDISP_RUN_DTYPE = np.dtype([(k, np.uint32) for k in ("kind", "first_frame", "op_begin", "q_begin")])
+# struct wq_recdisp_counters: 152 bytes
+RECDISP_COUNTERS_DTYPE = np.dtype([(k, np.uint64) for k in
+                                   ("n_db",) + tuple("n_" + c for c in RCLS_NAMES) +
+                                   ("n_records_total", "n_records", "n_creates", "n_deletes", "n_drop_walk",
+                                    "n_drop_no_position", "n_drop_world", "n_drop_unpackable", "n_deferred_records",
+                                    "n_runs", "first_deferred", "overflow", "error")])
+
+
+class RecDispatchIn(ctypes.Structure):  # struct wq_recdisp_in: device pointers
+    _fields_ = [("frames", ctypes.c_void_p), ("frame_offsets", ctypes.c_void_p), ("n_frames", ctypes.c_uint64),
+                ("n_frame_bytes", ctypes.c_uint64), ("msg", ctypes.c_void_p), ("world", ctypes.c_void_p),
+                ("flags", ctypes.c_void_p), ("db_src", ctypes.c_void_p), ("n_db", ctypes.c_uint64),
+                ("now_us", ctypes.c_int64), ("free_handles", ctypes.c_void_p), ("n_free", ctypes.c_uint32),
+                ("handle_next", ctypes.c_uint32), ("max_records", ctypes.c_uint64)]
+
+
+RECDISP_OUT_ARRAYS = ("cls", "ops", "op_ref", "q_src", "q_world", "q_pos", "q_after", "defer", "runs")
+
+
+class RecDispatchOut(ctypes.Structure):  # struct wq_recdisp_out: device pointers, each nullable
+    _fields_ = [(k, ctypes.c_void_p) for k in RECDISP_OUT_ARRAYS] + \
+               [(k, ctypes.c_uint32) for k in ("ops_capacity", "defer_capacity", "runs_capacity", "pad_")]
+
+
+assert ctypes.sizeof(RecDispatchIn) == 104 and ctypes.sizeof(RecDispatchOut) == 88
+assert REC_OP_REF_DTYPE.itemsize == 32 and RECDISP_DEFER_DTYPE.itemsize == 8 and RECDISP_RUN_DTYPE.itemsize == 16
+assert RECDISP_COUNTERS_DTYPE.itemsize == 152
+
+
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]
 

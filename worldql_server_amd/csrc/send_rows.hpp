@@ -85,24 +85,26 @@ RowSpace rows_view(wq_router* h, const uint32_t* off, uint32_t n_peers, size_t n
 
 // ---- scans (temp storage in h->sort_tmp) ----
 
-int scan_sat(wq_router* h, const uint32_t* in, uint32_t* out, size_t n) {
+// Exclusive scan of in[0 .. n) under the associative `op` (it need not commute), from `zero`.
+template <class In, class T, class Op>
+int scan_excl(wq_router* h, In in, T* out, const T& zero, size_t n, Op op) {
     size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
+    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, zero, n, op, h->stream));
     WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, 0u, n, BudSatAdd(), h->stream));
+    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, zero, n, op, h->stream));
     return WQ_OK;
 }
 
-// Exclusive u64 scan of the n terms f(0 .. n).
+int scan_sat(wq_router* h, const uint32_t* in, uint32_t* out, size_t n) { return scan_excl(h, in, out, 0u, n, BudSatAdd()); }
+
+// Exclusive scan of the n terms f(0 .. n).
+template <class F, class T, class Op>
+int scan_terms(wq_router* h, const F& f, T* out, const T& zero, size_t n, Op op) {
+    return scan_excl(h, rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), f), out, zero, n, op);
+}
 template <class F>
 int scan_terms(wq_router* h, const F& f, uint64_t* out, size_t n) {
-    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), f);
-    size_t bytes = 0;
-    WQ_HIP(h, rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), h->stream));
-    WQ_ALLOC(h, h->sort_tmp, bytes);
-    WQ_HIP(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                      h->stream));
-    return WQ_OK;
+    return scan_terms(h, f, out, (uint64_t)0, n, rocprim::plus<uint64_t>());
 }
 
 // The size of ordinal q, 0 behind the *T ordinals and, with flag words, where its flag is not set.

@@ -128,6 +128,19 @@ int ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, ui
     return WQ_OK;
 }
 
+// The handle's two tables as the kernels take them (the record dispatch looks worlds up in the same one).
+void ingest_tables(const wq_router* h, DecTables* t) {
+    t->n_worlds = h->frm_n_worlds;
+    t->world_bytes = h->frm_n_worlds ? h->frm_world_bytes.as<uint8_t>() + kDecWorldSlack : nullptr;
+    t->world_off = h->frm_world_off.as<uint32_t>();
+    t->world_hash = h->ing_whash.as<uint64_t>();
+    t->world_id = h->ing_wid.as<uint32_t>();
+    t->n_peers = h->ing_n_peers;
+    t->peer_hi = h->ing_phi.as<uint64_t>();
+    t->peer_lo = h->ing_plo.as<uint64_t>();
+    t->peer_id = h->ing_pid.as<uint32_t>();
+}
+
 // The call on device arrays (the handle's device is current; arguments validated, n_frames < 2^32 - 1).
 int launch_frames_decode(wq_router* h, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
                          size_t n_frame_bytes, const wq_ingest_out* out, wq_ingest_counters* d_counters) {
@@ -141,15 +154,7 @@ int launch_frames_decode(wq_router* h, const uint8_t* d_frames, const uint64_t* 
     if (n_frames) {
         DecList list{h->ing_list.as<DecEntry>(), reinterpret_cast<uint32_t*>(h->ing_ctrl.as<uint8_t>() + 64), cap};
         DecTables t;
-        t.n_worlds = h->frm_n_worlds;
-        t.world_bytes = h->frm_n_worlds ? h->frm_world_bytes.as<uint8_t>() + kDecWorldSlack : nullptr;
-        t.world_off = h->frm_world_off.as<uint32_t>();
-        t.world_hash = h->ing_whash.as<uint64_t>();
-        t.world_id = h->ing_wid.as<uint32_t>();
-        t.n_peers = h->ing_n_peers;
-        t.peer_hi = h->ing_phi.as<uint64_t>();
-        t.peer_lo = h->ing_plo.as<uint64_t>();
-        t.peer_id = h->ing_pid.as<uint32_t>();
+        ingest_tables(h, &t);
         uint32_t* word = h->ing_word.as<uint32_t>();
         const unsigned blocks = (unsigned)((n_frames + kDecBlock - 1) / kDecBlock);
         hipLaunchKernelGGL(k_decode_walk, dim3(blocks), dim3(kDecBlock), 0, s, d_frames, d_frame_offsets,

@@ -186,6 +186,8 @@ struct ExportWs {
 struct ShardCtx;  // shard_ctx.hpp: the exchange a sharded tick uses, and its workspace
 struct MultiCtx;  // wq_multi.hip: a handle over G GPUs (wq_router_create_multi)
 struct RecStore;  // wq_records.hip: the record store (wq_records_open)
+struct RecCfg;    // record_ops.hpp: a store's configuration
+struct DecTables; // decode_ops.hpp: the handle's world and sender tables as the kernels take them
 
 }  // namespace wq
 
@@ -300,6 +302,10 @@ struct wq_router {
     // ingest dispatch (wq_dispatch.hip): per frame its class between the passes; one DspSum per 1,024
     // frames and the total behind them
     wq::DevBuf dsp_cls, dsp_sum;
+    // record dispatch (wq_recdispatch.hip): per listed frame its class, record count, vector, `after`, the
+    // counts' prefix and the frames' scanned sums; per granule of 64 records the flag words and the two
+    // prefixes; the counters
+    wq::DevBuf rdp, rdp_ctrl;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -441,6 +447,14 @@ void ingest_release(wq_router* h);
 int launch_ingest_dispatch(wq_router* h, const wq_dispatch_in* in, size_t n_frames, const wq_dispatch_out* out,
                            wq_dispatch_counters* d_counters);
 void dispatch_release(wq_router* h);
+// wq_recdispatch.hip: the record dispatch on device arrays (asynchronous; arguments validated, a store is
+// open) and the release of its scratch. It takes the tables from wq_decode.hip (ingest_tables) and the
+// open store's configuration from wq_records.hip (records_config: false without a store).
+int launch_records_dispatch(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,
+                            wq_recdisp_counters* d_counters);
+void recdispatch_release(wq_router* h);
+void ingest_tables(const wq_router* h, DecTables* t);
+bool records_config(const wq_router* h, RecCfg* cfg);
 // wq_records.hip: frees the record store.
 void records_release(wq_router* h);
 // wq_table_export.hip: frees the export's scratch.

@@ -1042,6 +1042,13 @@ void records_release(wq_router* h) {
     h->rec = nullptr;
 }
 
+// The open store's configuration, for the record dispatch's packability test; false without a store.
+bool records_config(const wq_router* h, RecCfg* cfg) {
+    if (!h->rec) return false;
+    *cfg = h->rec->cfg;
+    return true;
+}
+
 }  // namespace wq
 
 using namespace wq;

@@ -131,6 +131,7 @@ int wq_router_destroy(wq_router* h) {
     frames_release(h);
     ingest_release(h);
     dispatch_release(h);
+    recdispatch_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -819,6 +820,24 @@ int wq_ingest_dispatch_device(wq_router* h, const wq_dispatch_in* in, size_t n_f
     if (n_frames >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_dispatch: n_frames must be < 2^32 - 1");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_ingest_dispatch(h, in, n_frames, out, d_counters);
+}
+
+int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,
+                               wq_recdisp_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!in || !out) return set_error(h, WQ_E_INVALID, "records_dispatch: in or out is null");
+    if (h->multi || !h->rec) return set_error(h, WQ_E_INVALID, "records_dispatch: no record store is open (wq_records_open)");
+    if ((in->n_frames && (!in->frame_offsets || !in->msg || !in->world || !in->flags)) || (in->n_frame_bytes && !in->frames) ||
+        (in->n_free && !in->free_handles))
+        return set_error(h, WQ_E_INVALID, "records_dispatch: a null array with a non-zero size");
+    if (in->n_frames >= 0xFFFFFFFFull || in->n_db >= 0xFFFFFFFFull)
+        return set_error(h, WQ_E_INVALID, "records_dispatch: n_frames and n_db must be < 2^32 - 1");
+    if (in->max_records >= 0xFFFFFFC0ull) return set_error(h, WQ_E_INVALID, "records_dispatch: max_records must be < 2^32 - 64");
+    if ((out->ops || out->op_ref) != (out->ops_capacity != 0) || !out->defer != !out->defer_capacity ||
+        !out->runs != !out->runs_capacity)
+        return set_error(h, WQ_E_INVALID, "records_dispatch: an array and its capacity are given together or not at all");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_records_dispatch(h, in, out, d_counters);
 }
 
 int wq_debug_set_ingest_list(wq_router* h, int64_t entries) {

@@ -14,6 +14,12 @@ classes of the header's table, the compact rows, the side lists and the run tabl
 the dict `decode_frames_np` returns. `IngestTick.dispatch` enqueues the device call on the decode's
 arrays and `IngestTick.process` reads the counters and the run table, the tick's one read-back, and
 issues the runs in order.
+
+`records_dispatch_np` is the definition of what wq_records_dispatch_device writes (csrc/wq_recdispatch.hip):
+the record frames of the dispatch's database list walked record by record into the ops and query rows of
+the record store, the deferred list and the run table that reproduces records.RecordProcessor.process's
+calls. `IngestTick.records_dispatch` enqueues the device call on the arrays decode() and dispatch() left;
+records.DeviceRecordProcessor issues its runs on a GpuRecordStore.
 """
 from __future__ import annotations
 
@@ -22,7 +28,7 @@ import uuid as _uuid
 
 import numpy as np
 
-from . import abi, codec
+from . import abi, codec, records as rec
 from .abi import (INGEST_COUNTERS_DTYPE, INGEST_ERROR_HUGE as ERROR_HUGE, INGEST_ERROR_OFFSETS as ERROR_OFFSETS,  # noqa: F401
                   INGEST_HAS_FLEX as HAS_FLEX, INGEST_HAS_PARAMETER as HAS_PARAMETER,
                   INGEST_HAS_POSITION as HAS_POSITION, INGEST_NO_PEER as NO_PEER, INGEST_OK as OK,
@@ -263,6 +269,306 @@ def dispatch_counters(raw) -> dict:
     return {k: [int(v) for v in c[k]] if k == "side_begin" else int(c[k]) for k in abi.DISPATCH_COUNTERS_DTYPE.names}
 
 
+# ---- the record dispatch: the record frames of a tick to store ops and queries (wq_records_dispatch_device) ----
+_VT_RECORDS = 14                                              # Message.records' vtable slot
+_VT_REC_UUID, _VT_REC_POS, _VT_REC_WORLD, _VT_REC_DATA, _VT_REC_FLEX = 4, 6, 8, 10, 12   # Record's slots
+_INS_CREATE, _INS_READ, _INS_DELETE = 8, 9, 11
+NO_AFTER = -(1 << 63)
+_MAX_SECONDS = 8_210_298_412_799                              # chrono's last second
+
+
+class _WalkError(Exception):
+    """The bounded reader refused an access (decode_ops.hpp DecV::fail)."""
+
+
+class _Reader:
+    """decode_ops.hpp's DecV over one frame: every access aligned and inside b[0 .. n), or _WalkError."""
+
+    def __init__(self, b: bytes):
+        self.b, self.n, self.apparent, self.tables, self.depth = b, len(b), 0, 0, 0
+
+    def aligned(self, pos, a):
+        if pos % a:
+            raise _WalkError
+
+    def range(self, pos, size):
+        self.apparent += size
+        if pos + size > self.n or self.apparent > 1 << 31:
+            raise _WalkError
+
+    def u32_at(self, pos):
+        self.aligned(pos, 4)
+        self.range(pos, 4)
+        return struct.unpack_from("<I", self.b, pos)[0]
+
+    def u16_at(self, pos):
+        self.aligned(pos, 2)
+        self.range(pos, 2)
+        return struct.unpack_from("<H", self.b, pos)[0]
+
+    def follow(self, pos):
+        return pos + self.u32_at(pos)
+
+    def vec_range(self, pos, elem):
+        n = self.u32_at(pos)
+        self.aligned(pos + 4, elem)
+        self.range(pos + 4, n * elem)
+        return pos + 4, n
+
+    def visit_table(self, pos):
+        self.tables += 1
+        so = self.u32_at(pos)
+        so -= (so >> 31) << 32          # as i32
+        if so > pos:
+            raise _WalkError
+        vt = pos - so
+        if vt >= self.n:
+            raise _WalkError
+        vl = self.u16_at(vt)
+        self.aligned(vt + vl, 2)
+        self.range(vt, vl)
+        self.depth += 1
+        return pos, vt, vl
+
+    def field(self, t, voff):
+        pos, vt, vl = t
+        fo = self.u16_at(vt + voff) if voff < vl else 0
+        return pos + fo if fo else 0
+
+    def field_bytes(self, t, voff):
+        """(offset, length) of a byte vector or a string, None when absent."""
+        fp = self.field(t, voff)
+        if not fp:
+            return None
+        vp = self.follow(fp)
+        self.aligned(vp, 4)
+        return self.vec_range(vp, 1)
+
+    def field_vec3(self, t, voff):
+        fp = self.field(t, voff)
+        if fp:
+            self.range(fp, 24)
+        return fp or None
+
+
+def parse_after(s: bytes):
+    """utils/time.rs:6-16 digit by digit: u64::from_str (an optional '+', digits only, below 2^64), then
+    chrono's range. Microseconds, or None when it does not parse."""
+    i = 1 if s[:1] == b"+" else 0
+    if i == len(s):
+        return None
+    v = 0
+    for c in s[i:]:
+        if not 0x30 <= c <= 0x39:
+            return None
+        v = v * 10 + (c - 0x30)
+        if v >= 1 << 64:
+            return None
+    return None if v // 1000 > _MAX_SECONDS else v * 1000
+
+
+def parse_uuid_text(s: bytes):
+    """uuid 0.8.2 Uuid::parse_str as the decoder restates it: 32 hex digits, the hyphenated form, or that
+    behind "urn:uuid:". The value, or None."""
+    if len(s) == 45 and s[:9] == b"urn:uuid:":
+        s = s[9:]
+    elif len(s) not in (32, 36):
+        return None
+    if len(s) == 36:
+        if any(s[k] != 0x2D for k in (8, 13, 18, 23)):
+            return None
+        s = s[:8] + s[9:13] + s[14:18] + s[19:23] + s[24:]
+    if len(s) != 32 or any(c not in b"0123456789abcdefABCDEF" for c in s):
+        return None
+    return int(s, 16)
+
+
+def _sanitized(name: bytes):
+    """The sanitized name as bytes, None when the sanitizer refuses it (bytes that are no UTF-8 hold a
+    character outside its set)."""
+    try:
+        return sanitize_world_name(name.decode("utf-8")).encode("utf-8")
+    except (SanitizeError, UnicodeDecodeError):
+        return None
+
+
+def _frame_bytes(data, off, f, n, nb):
+    """Frame f's bytes under decode_frames_np's rules for offsets, None when they are refused."""
+    a, b = off[f], off[f + 1]
+    if a > b or b > nb or (f > 0 and off[f - 1] > a) or (f + 1 < n and b > off[f + 2]) or b - a >= 1 << 32:
+        return None
+    return data[a:b].tobytes()
+
+
+def _record(rd: _Reader, vec, r, ids, sizes):
+    """(status, fields) of record r of the vector at vec: "walk", "no_position", "world", "unpackable",
+    "defer" or "accept" (csrc/recdispatch_ops.hpp rd_record)."""
+    try:
+        t = rd.visit_table(rd.follow(vec + 4 * r))
+        uuid = rd.field_bytes(t, _VT_REC_UUID)
+        at = rd.field_vec3(t, _VT_REC_POS)
+        world = rd.field_bytes(t, _VT_REC_WORLD)
+        data = rd.field_bytes(t, _VT_REC_DATA)
+        flex = rd.field_bytes(t, _VT_REC_FLEX)
+        if uuid is None or world is None:
+            raise _WalkError
+        u = parse_uuid_text(rd.b[uuid[0]:uuid[0] + uuid[1]])
+        if u is None:
+            raise _WalkError
+    except _WalkError:
+        return "walk", None
+    if at is None:
+        return "no_position", None
+    name = _sanitized(rd.b[world[0]:world[0] + world[1]])
+    if name is None:
+        return "world", None
+    w = ids.get(name)
+    if w is None:
+        return "defer", None
+    bits = struct.unpack_from("<3Q", rd.b, at)
+    if not rec.position_packable(sizes, w, struct.unpack_from("<3d", rd.b, at)):
+        return "unpackable", None
+    ref = (data or (0, 0)) + (flex or (0, 0)) + ((1 if data else 0) | (2 if flex else 0),)
+    return "accept", (w, bits, u >> 64, u & ((1 << 64) - 1), ref)
+
+
+def records_dispatch_np(frames, offsets, decoded, db_src, store_sizes, world_names, now_us, free_handles=None,
+                        handle_next=0, ops_capacity=None, defer_capacity=None, runs_capacity=None, max_records=None,
+                        n_frame_bytes=None):
+    """The definition of wq_records_dispatch_device: the header's frame rules, record rules and runs in plain
+    Python over the raw frames, the dict decode_frames_np returns (msg, world, flags) and the dispatch's
+    database list (db_src None: every frame). The host decoder reports only a frame's record count, so the
+    records are walked here with a bounded reader that restates the device's. store_sizes: the open
+    store's three region sizes; world_names: the table of Router.set_worlds.
+
+    Returns a dict of cls u8[n_db], ops (records.REC_OP_DTYPE) / op_ref (abi.REC_OP_REF_DTYPE), cut at
+    ops_capacity, the query rows q_src / q_world / q_pos (f64[k, 3], the bits copied) / q_after, defer
+    (abi.RECDISP_DEFER_DTYPE, cut at defer_capacity), runs (abi.RECDISP_RUN_DTYPE: the first min(n_runs + 1,
+    runs_capacity) entries, the closing one included) and counters (abi.RECDISP_COUNTERS_DTYPE's fields).
+    A capacity of None holds everything; max_records None examines every record."""
+    data = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    off = [int(v) for v in np.asarray(offsets, dtype=np.uint64).reshape(-1)]
+    n = max(len(off) - 1, 0)
+    nb = len(data) if n_frame_bytes is None else int(n_frame_bytes)
+    msg, world_a, flags_a = decoded["msg"], np.asarray(decoded["world"], np.uint32), np.asarray(decoded["flags"], np.uint8)
+    src = list(range(n)) if db_src is None else [int(v) for v in db_src]
+    ids = world_ids(world_names)
+    sizes = tuple(int(s) for s in store_sizes)
+    free = [] if free_handles is None else [int(v) for v in free_handles]
+    limit = None if max_records is None else int(max_records)
+    cnt = {k: 0 for k in abi.RECDISP_COUNTERS_DTYPE.names}
+    cls = np.zeros(len(src), np.uint8)
+    ops, refs, q, defer, runs = [], [], [], [], []
+    error, open_run, examined, creates, first_def = 0, abi.RRUN_END, 0, 0, None
+    for j, f in enumerate(src):
+        if j and src[j - 1] >= f:
+            error |= abi.RECDISP_ERROR_LIST
+        if f >= n:
+            error |= abi.RECDISP_ERROR_LIST
+            continue
+        b = _frame_bytes(data, off, f, n, nb)
+        if b is None:
+            error |= abi.RECDISP_ERROR_WALK
+            continue
+        flags, m = int(flags_a[f]), msg[f]
+        ins = int(m["instruction"])
+        if not flags & OK or flags & WORLD_IS_GLOBAL or ins not in _INS_DB:
+            continue
+        rd = _Reader(b)
+        n_ops, n_q = len(ops), len(q)
+        if ins != _INS_READ:   # record_create.rs / record_delete.rs: every record carries its own world
+            c, kind = abi.RCLS_APPLY, abi.RRUN_APPLY
+            try:
+                fp = rd.field(rd.visit_table(rd.follow(0)), _VT_RECORDS)
+                vec, count = (0, 0)
+                if fp:
+                    vp = rd.follow(fp)
+                    rd.aligned(vp, 4)
+                    vec, count = rd.vec_range(vp, 4)
+            except _WalkError:
+                error |= abi.RECDISP_ERROR_WALK
+                vec, count = 0, 0
+            cnt["n_records_total"] += count
+            for r in range(count):
+                if limit is not None and examined >= limit:
+                    break
+                examined += 1
+                status, got = _record(_Reader(b), vec, r, ids, sizes)
+                if status == "accept":
+                    w, bits, hi, lo, ref = got
+                    handle = 0
+                    if ins == _INS_CREATE:
+                        handle = free[creates] if creates < len(free) else (handle_next + creates - len(free)) & 0xFFFFFFFF
+                        creates += 1
+                    ops.append((rec.CREATE if ins == _INS_CREATE else rec.DELETE, w, bits, hi, lo, now_us, handle))
+                    refs.append((f, r) + ref + (0,))
+                    cnt["n_creates" if ins == _INS_CREATE else "n_deletes"] += 1
+                elif status == "defer":
+                    defer.append((f, r))
+                    cnt["n_deferred_records"] += 1
+                    first_def = f if first_def is None else min(first_def, f)
+                else:
+                    cnt[{"walk": "n_drop_walk", "no_position": "n_drop_no_position", "world": "n_drop_world",
+                         "unpackable": "n_drop_unpackable"}[status]] += 1
+                    error |= abi.RECDISP_ERROR_WALK if status == "walk" else 0
+        else:                   # record_read.rs:18-41
+            c, kind, after = abi.RCLS_READ_DROPPED, abi.RRUN_READ, NO_AFTER
+            ok = bool(flags & HAS_POSITION)
+            if ok and flags & HAS_PARAMETER:
+                p0, pl = int(m["param_off"]), int(m["param_len"])
+                if p0 + pl > len(b):
+                    error |= abi.RECDISP_ERROR_WALK
+                    ok = False
+                else:
+                    after = parse_after(b[p0:p0 + pl])
+                    ok = after is not None
+            if ok:
+                w0, wl = int(m["world_off"]), int(m["world_len"])
+                if w0 + wl > len(b):
+                    error |= abi.RECDISP_ERROR_WALK
+                    ok = False
+                else:
+                    ok = _sanitized(b[w0:w0 + wl]) is not None
+            if ok and flags & WORLD_KNOWN and int(world_a[f]) < abi.WORLD_GLOBAL:
+                c = abi.RCLS_READ
+                q.append((f, int(world_a[f]), np.array(m["position"], np.float64).view(np.uint64).tolist(), after))
+            elif ok:
+                c = abi.RCLS_READ_DEFERRED
+                defer.append((f, abi.RDEFER_READ))
+                first_def = f if first_def is None else min(first_def, f)
+        cls[j] = c
+        if open_run != kind:                         # a barrier: process flushes the other kind's batch
+            open_run = abi.RRUN_END
+        if len(ops) > n_ops or len(q) > n_q:         # effective: it joins its kind's open batch or starts one
+            if open_run != kind:
+                runs.append((kind, f, n_ops, n_q))
+            open_run = kind
+    n_runs = len(runs)
+    runs.append((abi.RRUN_END, n, len(ops), len(q)))
+    caps = [len(ops) if ops_capacity is None else int(ops_capacity), len(defer) if defer_capacity is None else int(defer_capacity),
+            n_runs + 1 if runs_capacity is None else int(runs_capacity)]
+    cnt.update(n_db=len(src), n_records=examined, n_runs=n_runs, first_deferred=n if first_def is None else first_def, error=error)
+    for k, name in enumerate(abi.RCLS_NAMES):
+        cnt["n_" + name] = int((cls == k).sum())
+    cnt["overflow"] = (abi.RECDISP_OVERFLOW_OPS if len(ops) > caps[0] else 0) | \
+        (abi.RECDISP_OVERFLOW_DEFER if len(defer) > caps[1] else 0) | (abi.RECDISP_OVERFLOW_RUNS if n_runs + 1 > caps[2] else 0) | \
+        (abi.RECDISP_OVERFLOW_RECORDS if limit is not None and cnt["n_records_total"] > limit else 0)
+    op_a = np.zeros(min(len(ops), caps[0]), dtype=rec.REC_OP_DTYPE)
+    for i, (k, w, bits, hi, lo, t, hd) in enumerate(ops[:caps[0]]):
+        op_a[i] = (k, w, np.array(bits, np.uint64).view(np.float64), hi, lo, t, hd, 0)
+    q_pos = np.array([r[2] for r in q], dtype=np.uint64).reshape(-1, 3).view(np.float64)
+    return dict(cls=cls, ops=op_a, op_ref=np.array(refs[:caps[0]], dtype=abi.REC_OP_REF_DTYPE).reshape(-1),
+                q_src=np.array([r[0] for r in q], np.uint32), q_world=np.array([r[1] for r in q], np.uint32), q_pos=q_pos,
+                q_after=np.array([r[3] for r in q], np.int64), defer=np.array(defer[:caps[1]], dtype=abi.RECDISP_DEFER_DTYPE).reshape(-1),
+                runs=np.array(runs[:min(n_runs + 1, caps[2])], dtype=abi.RECDISP_RUN_DTYPE).reshape(-1), counters=cnt)
+
+
+def records_dispatch_counters(raw) -> dict:
+    """abi.RECDISP_COUNTERS_DTYPE bytes as records_dispatch_np's counters dict."""
+    c = np.asarray(raw).view(np.uint8)[:abi.RECDISP_COUNTERS_DTYPE.itemsize].view(abi.RECDISP_COUNTERS_DTYPE)[0]
+    return {k: int(c[k]) for k in abi.RECDISP_COUNTERS_DTYPE.names}
+
+
 class IngestTick:
     """The device arrays of one tick's decode, grow-only, and the step from received frames to
     Router.route_device: decode(frames, offsets) enqueues wq_frames_decode_device, route(...) the tick on
@@ -449,3 +755,107 @@ class IngestTick:
             a = self.dbuf[k][:rows * w].cpu().numpy().view(self._DTYPES[k])
             got[k] = a.reshape(rows, 3) if k == "l_pos" else a
         return got
+
+    # ---- the record dispatch: the tick's record frames to store ops and queries (wq_records_dispatch_device) ----
+    _RSPEC = dict(cls=(1, np.uint8), ops=(64, rec.REC_OP_DTYPE), op_ref=(32, abi.REC_OP_REF_DTYPE), q_src=(4, np.uint32),
+                  q_world=(4, np.uint32), q_pos=(24, np.float64), q_after=(8, np.int64), defer=(8, abi.RECDISP_DEFER_DTYPE))
+    _RCSIZE = abi.RECDISP_COUNTERS_DTYPE.itemsize
+
+    def records_dispatch(self, frames, offsets, now_us: int, free_handles=None, handle_next: int = 0,
+                         max_records: int | None = None, ops_capacity: int | None = None, defer_capacity: int | None = None,
+                         runs_capacity: int | None = None, counters: dict | None = None) -> "IngestTick":
+        """Enqueues wq_records_dispatch_device on the arrays decode() and dispatch() left: frames / offsets are the
+        device tensors decode() took, db_src is the database segment of the dispatch's side_src, taken where it
+        lies once the dispatch's counters are known (`counters`, else one read of them). free_handles: the
+        handles the call's creates take first (a sequence of u32), then handle_next onwards. max_records
+        defaults to frames.numel() // 4, which always suffices; the capacities default to what holds
+        everything under that bound. The router needs an open record store. Nothing is read back here."""
+        import torch
+        cnt = counters if counters is not None else self._read_ctrl()[0]
+        sb = cnt["side_begin"]
+        n_db = sb[3] - sb[2]
+        nb = frames.numel()
+        limit = min(nb // 4, abi.RECDISP_MAX_RECORDS - 1) if max_records is None else int(max_records)
+        caps = dict(ops=limit if ops_capacity is None else ops_capacity,
+                    defer=limit + n_db if defer_capacity is None else defer_capacity,
+                    runs=n_db + 1 if runs_capacity is None else runs_capacity)
+        rows = dict(cls=n_db, ops=caps["ops"], op_ref=caps["ops"], q_src=n_db, q_world=n_db, q_pos=n_db, q_after=n_db,
+                    defer=caps["defer"])
+        if not hasattr(self, "rbuf"):
+            self.rbuf, self.rctrl = {}, None
+        for k, (w, _) in self._RSPEC.items():   # grow-only; empty, not zeros: a fill would run on torch's stream
+            if k not in self.rbuf or self.rbuf[k].numel() < max(rows[k] * w, 8):
+                self.rbuf[k] = torch.empty(max(2 * rows[k] * w, 8), dtype=torch.uint8, device=self.device)
+        if self.rctrl is None or self.rctrl.numel() < self._RCSIZE + 16 * caps["runs"]:
+            self.rctrl = torch.empty(self._RCSIZE + 32 * max(caps["runs"], 1), dtype=torch.uint8, device=self.device)
+        free = np.ascontiguousarray(free_handles if free_handles is not None else [], dtype=np.uint32)
+        # a copy from pageable host memory has landed when .to() returns, whatever stream it ran on
+        self.r_free = torch.from_numpy(free.view(np.int32).copy()).to(self.device) if len(free) else None
+        ptr = {k: (self.rbuf[k].data_ptr() if rows[k] or k in ("cls", "q_src", "q_world", "q_pos", "q_after") else None)
+               for k in self._RSPEC}
+        self.r_caps, self.r_rows, self.r_n_db = caps, rows, n_db
+        o = self.out
+        self.r_in = abi.RecDispatchIn(frames=frames.data_ptr() if nb else None, frame_offsets=offsets.data_ptr(),
+                                      n_frames=self.n, n_frame_bytes=nb, msg=o.msg, world=o.world, flags=o.flags,
+                                      db_src=self.d_out.side_src + 4 * sb[2], n_db=n_db, now_us=now_us,
+                                      free_handles=None if self.r_free is None else self.r_free.data_ptr(), n_free=len(free),
+                                      handle_next=handle_next, max_records=limit)
+        self.r_out = abi.RecDispatchOut(**ptr, runs=self.rctrl.data_ptr() + self._RCSIZE if caps["runs"] else None,
+                                        ops_capacity=caps["ops"], defer_capacity=caps["defer"], runs_capacity=caps["runs"])
+        self.router.records_dispatch_device(self.r_in, self.r_out, self.rctrl.data_ptr())
+        return self
+
+    def read_records_ctrl(self):
+        """The record dispatch's counters and run table: one copy. Waits for the device first."""
+        import torch
+        torch.cuda.synchronize()
+        raw = self.rctrl[:self._RCSIZE + 16 * self.r_caps["runs"]].cpu().numpy()
+        cnt = records_dispatch_counters(raw)
+        have = min(cnt["n_runs"] + 1, self.r_caps["runs"])
+        return cnt, raw[self._RCSIZE:self._RCSIZE + 16 * have].copy().view(abi.RECDISP_RUN_DTYPE)
+
+    def read_records_rows(self, k: str, lo: int, hi: int) -> np.ndarray:
+        """Rows [lo, hi) of the record dispatch's output k (after read_records_ctrl: the device has finished)."""
+        w, dt = self._RSPEC[k]
+        a = self.rbuf[k][lo * w:hi * w].cpu().numpy().view(dt)
+        return a.reshape(-1, 3) if k == "q_pos" else a
+
+    def read_records_dispatch(self) -> dict:
+        """Every output of the record dispatch and the counters as numpy arrays shaped like
+        records_dispatch_np's (synchronizes; for tests)."""
+        cnt, runs = self.read_records_ctrl()
+        n_ops = min(cnt["n_creates"] + cnt["n_deletes"], self.r_caps["ops"])
+        n_def = min(cnt["n_deferred_records"] + cnt["n_read_deferred"], self.r_caps["defer"])
+        have = dict(cls=cnt["n_db"], ops=n_ops, op_ref=n_ops, q_src=cnt["n_read"], q_world=cnt["n_read"], q_pos=cnt["n_read"],
+                    q_after=cnt["n_read"], defer=n_def)
+        got = {k: self.read_records_rows(k, 0, n) for k, n in have.items()}
+        got.update(counters=cnt, runs=runs)
+        return got
+
+    def read_msg_rows(self, frames_idx) -> np.ndarray:
+        """The decoder's msg structs of the given frames (after a read that waited for the device)."""
+        import torch
+        idx = torch.as_tensor(np.asarray(frames_idx, np.int64), device=self.device)
+        return self.buf["msg"][:self.n * 72].view(self.n, 72)[idx].cpu().numpy().reshape(-1).view(codec.DECODED_DTYPE)
+
+
+def deferred_event(frame: bytes, m, record: int) -> dict:
+    """One entry of the record dispatch's deferred list as an event of records.RecordProcessor: the read
+    (record == abi.RDEFER_READ) or the frame's create / delete with that one record, taken from a frame the
+    decoder accepted (m: its msg struct)."""
+    w0, p0 = int(m["world_off"]), int(m["param_off"])
+    event = dict(instruction={_INS_CREATE: "RecordCreate", _INS_READ: "RecordRead", _INS_DELETE: "RecordDelete"}[int(m["instruction"])],
+                 world_name=frame[w0:w0 + int(m["world_len"])].decode("utf-8"), sender_uuid=_uuid.UUID(bytes=bytes(m["sender_uuid"])),
+                 parameter=frame[p0:p0 + int(m["param_len"])].decode("utf-8") if m["has_parameter"] else None,
+                 position=tuple(float(c) for c in m["position"]) if m["has_position"] else None, records=[])
+    if record != abi.RDEFER_READ:
+        rd = _Reader(frame)
+        vec, _ = rd.vec_range(rd.follow(rd.field(rd.visit_table(rd.follow(0)), _VT_RECORDS)), 4)
+        t = rd.visit_table(rd.follow(vec + 4 * record))
+        text = lambda r: None if r is None else frame[r[0]:r[0] + r[1]]   # noqa: E731
+        u = parse_uuid_text(text(rd.field_bytes(t, _VT_REC_UUID)))
+        at, data = rd.field_vec3(t, _VT_REC_POS), text(rd.field_bytes(t, _VT_REC_DATA))
+        event["records"] = [dict(uuid=(u >> 64, u & ((1 << 64) - 1)), world_name=text(rd.field_bytes(t, _VT_REC_WORLD)).decode("utf-8"),
+                                 position=struct.unpack_from("<3d", frame, at) if at else None,
+                                 data=None if data is None else data.decode("utf-8"), flex=text(rd.field_bytes(t, _VT_REC_FLEX)))]
+    return event

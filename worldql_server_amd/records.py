@@ -4,7 +4,8 @@
 (worldql_server/src/database/client.rs, world_region.rs, query_constants.rs) and
 handle_record_read (processing/record_read.rs) restated, with what the reference leaves open
 fixed as the header says. `GpuRecordStore` is the ctypes binding of the wq_records_* calls and
-`RecordProcessor` the host side of the three instructions around it.
+`RecordProcessor` the host side of the three instructions around it. `DeviceRecordProcessor` is the same
+with the per-record work on the device (wq_records_dispatch_device through ingest.IngestTick).
 """
 from __future__ import annotations
 
@@ -633,6 +634,144 @@ class RecordProcessor:
                 self.store.vacuum()
                 self.vacuums += 1
         return replies
+
+    def _free_dead(self):
+        for hd in self.store.drain_dead():
+            self.slab[int(hd)] = None
+            self.free.append(int(hd))
+
+
+class DeviceRecordProcessor:
+    """RecordProcessor with the per-record work on the device: a tick's frames go through the decoder, the
+    dispatch and wq_records_dispatch_device (ingest.IngestTick), and the host is left with one read of the
+    counters, the run table and the payload references, the copy of the created records' payloads into the
+    slab, and the store calls in run order on a GpuRecordStore: apply_device on slices of the ops,
+    read_device on slices of the query rows (a sizing call, then the answering call, as
+    RecordProcessor.process's read_batch). The slab and the free list are RecordProcessor's; the call's
+    creates take the free handles in the order RecordProcessor would pop them, then the slab's end.
+
+    A tick is exact up to the dispatch's first_deferred: records and reads whose world name the handle's
+    table does not hold are listed by the device and handed, after the tick's runs, to a RecordProcessor
+    over the same store, slab and free list; the names it interns are added to the router's table, so the
+    next tick resolves them on the device. A slab entry holds the record's uuid, position, data and flex;
+    its world_name is the sanitized name."""
+
+    def __init__(self, store, tick, world_names, dedupe: bool = True):
+        self.store, self.tick, self.router, self.dedupe = store, tick, store.router, dedupe
+        self.names = [n if isinstance(n, str) else bytes(n).decode("utf-8") for n in world_names]
+        self.fallback = RecordProcessor(store, WorldIds(), dedupe)
+        for n in self.names:
+            self.fallback.worlds.intern(n)
+        self.slab, self.free = self.fallback.slab, self.fallback.free   # shared with the fallback
+        self.deferred = 0
+        self.sizing_rejected = 0   # queries the sizing calls rejected: the answering calls count them again
+        self.last_counters: dict = {}
+
+    def totals(self) -> dict:
+        """The store's totals with every rejected query of the device's runs counted once, as a store that is
+        asked once counts them (the sizing call and the answering call both reject it)."""
+        t = self.store.totals()
+        t["rejected_queries"] -= self.sizing_rejected
+        return t
+
+    def process(self, data, offsets, now_us: int, d_frames=None, d_offsets=None) -> list:
+        """One tick of frames (data u8, offsets u64[n + 1], host arrays; d_frames / d_offsets: the same on
+        the device when the caller has uploaded them). Returns RecordProcessor.process's replies:
+        [(sender_uuid, world_name, records)]."""
+        import torch
+        from . import ingest
+        tick, dev = self.tick, self.tick.device
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if d_frames is None:
+            d_frames = torch.from_numpy(data.copy() if len(data) else np.zeros(1, np.uint8)).to(dev)[:len(data)]
+            d_offsets = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
+        tick.decode(d_frames, d_offsets).dispatch()
+        tick.records_dispatch(d_frames, d_offsets, now_us, free_handles=self.free[::-1], handle_next=len(self.slab))
+        cnt, runs = tick.read_records_ctrl()
+        self.last_counters = cnt
+        if cnt["overflow"] or cnt["error"]:
+            raise ValueError(f"records dispatch: overflow {cnt['overflow']:#x}, error {cnt['error']:#x}")
+        n_ops, off = cnt["n_creates"] + cnt["n_deletes"], [int(v) for v in offsets]
+        frame = lambda f: data[off[f]:off[f + 1]].tobytes()   # noqa: E731
+
+        # the created records' payloads, under the handles the device gave them
+        if cnt["n_creates"]:
+            ops, refs = tick.read_records_rows("ops", 0, n_ops), tick.read_records_rows("op_ref", 0, n_ops)
+            taken = min(cnt["n_creates"], len(self.free))
+            del self.free[len(self.free) - taken:]
+            self.slab.extend([None] * (cnt["n_creates"] - taken))
+            cache = (-1, b"")
+            for op, ref in zip(ops, refs):
+                if op["kind"] != CREATE:
+                    continue
+                if cache[0] != ref["frame"]:
+                    cache = (int(ref["frame"]), frame(int(ref["frame"])))
+                b = cache[1]
+                self.slab[int(op["handle"])] = {
+                    "uuid": (int(op["uuid_hi"]), int(op["uuid_lo"])), "world_name": self.names[int(op["world"])],
+                    "position": tuple(float(c) for c in op["pos"]),
+                    "data": b[ref["data_off"]:ref["data_off"] + ref["data_len"]].decode("utf-8") if ref["bits"] & 1 else None,
+                    "flex": b[ref["flex_off"]:ref["flex_off"] + ref["flex_len"]] if ref["bits"] & 2 else None}
+
+        # the runs in order
+        replies, o = [], tick.r_out
+        q_src = tick.read_records_rows("q_src", 0, cnt["n_read"])
+        msg = tick.read_msg_rows(q_src) if cnt["n_read"] else None
+        for a, b in zip(runs[:-1], runs[1:]):
+            if a["kind"] == abi.RRUN_APPLY:
+                lo, hi = int(a["op_begin"]), int(b["op_begin"])
+                self.store.apply_device(o.ops + 64 * lo, hi - lo)
+                continue
+            lo, hi = int(a["q_begin"]), int(b["q_begin"])
+            replies += self._read(lo, hi, q_src, msg, frame)
+        self._free_dead()
+
+        # what the device deferred: the host's, after the tick
+        n_def = cnt["n_deferred_records"] + cnt["n_read_deferred"]
+        if n_def:
+            self.deferred += n_def
+            pairs = tick.read_records_rows("defer", 0, n_def)
+            frames_idx = sorted({int(p["frame"]) for p in pairs})
+            rows = dict(zip(frames_idx, tick.read_msg_rows(frames_idx)))
+            events = [ingest.deferred_event(frame(int(p["frame"])), rows[int(p["frame"])], int(p["record"])) for p in pairs]
+            replies += self.fallback.process(events, now_us)
+            if len(self.fallback.worlds) > len(self.names):
+                self.names = [self.fallback.worlds.name(w) for w in range(len(self.fallback.worlds))]
+                self.router.set_worlds(self.names)
+        return replies
+
+    def _read(self, lo: int, hi: int, q_src, msg, frame) -> list:
+        """One read run: rows [lo, hi) of the query arrays. A batch the store finds too large for one call is
+        answered in two halves, as RecordProcessor.process's read_batch."""
+        import torch
+        import uuid as _uuid
+        o, n = self.tick.r_out, hi - lo
+        d_off = torch.empty(n + 1, dtype=torch.int32, device=self.tick.device)
+        args = (n, o.q_world + 4 * lo, o.q_pos + 24 * lo, o.q_after + 8 * lo)
+        try:
+            sizing = self.store.read_device(*args, False, d_off.data_ptr(), 0, 0, 0)
+            need = sizing["returned"]
+            self.sizing_rejected += sizing["rejected"]
+            d_h = torch.empty(max(need, 1), dtype=torch.int32, device=self.tick.device)
+            d_ts = torch.empty(max(need, 1), dtype=torch.int64, device=self.tick.device)
+            self.store.read_device(*args, self.dedupe, d_off.data_ptr(), d_h.data_ptr() if need else 0,
+                                   d_ts.data_ptr() if need else 0, need)
+        except ReadTooLarge:
+            if n == 1:
+                raise
+            return self._read(lo, lo + n // 2, q_src, msg, frame) + self._read(lo + n // 2, hi, q_src, msg, frame)
+        off = d_off.cpu().numpy().view(np.uint32)
+        handles = d_h.cpu().numpy().view(np.uint32)
+        out = []
+        for i in range(n):
+            recs = [self.slab[int(hd)] for hd in handles[int(off[i]):int(off[i + 1])]]
+            if recs:
+                m = msg[lo + i]
+                b = frame(int(q_src[lo + i]))
+                w0 = int(m["world_off"])
+                out.append((_uuid.UUID(bytes=bytes(m["sender_uuid"])), b[w0:w0 + int(m["world_len"])].decode("utf-8"), recs))
+        return out
 
     def _free_dead(self):
         for hd in self.store.drain_dead():

@@ -92,6 +92,7 @@ def load_library(build_if_missing: bool = True):
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
+        "wq_records_dispatch_device": ([vp, ctypes.POINTER(abi.RecDispatchIn), ctypes.POINTER(abi.RecDispatchOut), vp], i32),
         "wq_records_open": ([vp, u16, u16, u16, u32], i32),
         "wq_records_close": ([vp], i32),
         "wq_records_apply": ([vp, vp, sz, vp], i32),
@@ -514,6 +515,19 @@ class Router:
         self._check(self.lib.wq_ingest_dispatch_device(self.h, ctypes.byref(src) if src is not None else None, n_frames,
                                                        ctypes.byref(out) if out is not None else None,
                                                        counters_ptr or None))
+
+    def records_dispatch_device(self, src: "abi.RecDispatchIn", out: "abi.RecDispatchOut",
+                                counters_ptr: int | None = None) -> None:
+        """wq_records_dispatch_device: the record frames of a decoded tick (abi.RecDispatchIn: the raw frames,
+        the decode's msg / world / flags, the dispatch's database list, the handle allocator) walked record
+        by record into the device arrays of `out` (abi.RecDispatchOut, each nullable): the ops of
+        GpuRecordStore.apply_device with their payload references, the query rows of read_device, the
+        deferred list and the run table. Needs an open record store (its region sizes decide what is
+        packable). Asynchronous on the handle's stream; the counters (abi.RECDISP_COUNTERS_DTYPE) stay
+        where counters_ptr points. Host definition: ingest.records_dispatch_np."""
+        self._check(self.lib.wq_records_dispatch_device(self.h, ctypes.byref(src) if src is not None else None,
+                                                        ctypes.byref(out) if out is not None else None,
+                                                        counters_ptr or None))
 
     def set_ingest_list(self, entries: int) -> None:
         """wq_debug_set_ingest_list: a test hook, the long-string work list's capacity (0: none; negative:
