@@ -1626,6 +1626,112 @@ typedef struct wq_recdisp_counters {
 int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,
                                wq_recdisp_counters* d_counters /* nullable */);
 
+/* ---- record payload slab: the created records' payloads kept in device memory ----
+ * wq_records_dispatch_device leaves, per accepted create, an op with the caller's payload slot (`handle`) and
+ * an op_ref that says where the record's data and flex lie inside its frame. records.DeviceRecordProcessor
+ * reads both back and slices the frames on the host, one Python dict per record. Here one call copies the
+ * payloads from the frames where they lie into an arena in device memory and writes one 64-byte entry per
+ * handle. The memory is the caller's (it grows it); the view describes it. Nothing is read back. The host
+ * definition is records.slab_store_np.
+ *
+ *   - Every op of kind WQ_RECORD_CREATE writes entries[op.handle]: uuid = the big-endian bytes of uuid_hi
+ *     then uuid_lo (the uuid's 16 bytes as the decoder parsed them from the text), pos and world as the op
+ *     holds them, bits 0 and 1 from op_ref.bits, bit 2 (position) and bit 31 (live) set, and data_len /
+ *     flex_len. Its data lies at payload[off .. off + data_len) and its flex directly behind it. Ops of any
+ *     other kind are skipped. A payload whose bit is clear has length 0 whatever op_ref's length says.
+ *   - Placement: the u64 exclusive scan of data_len + flex_len over the ops in op order, starting at
+ *     *d_cursor, a device word the call advances by the total. No padding between payloads.
+ *   - All or nothing. With *d_cursor + total > n_payload_bytes (overflow bit 0) or a create whose handle is
+ *     >= n_entries (overflow bit 1) no entry and no payload byte is written and the cursor stays; bytes_need
+ *     is the arena size and entries_need the entry count that suffice. The caller grows and calls again.
+ *   - Hostile references (never a fault). frame_offsets[n_frames] is taken as the size of d_frames. error
+ *     bit 0: op_ref.frame >= n_frames, or that frame's offsets descend or pass frame_offsets[n_frames]: both
+ *     payloads present as op_ref.bits says, and empty. Bit 1: the data range leaves its frame (off + len in
+ *     u64): data empty. Bit 2: the same for flex. The handles of one call's creates are distinct, as the
+ *     dispatch's allocator gives them; of two creates with one handle the entry is either's.
+ *   - The copy runs over the arena's bytes [cursor, cursor + total) like wq_peer_pack_device's: a wave owns
+ *     a 1 KiB-aligned tile of the arena and a lane one 16-byte store, so a 1 MiB flex spreads over the
+ *     grid and empty payloads cost nothing. Only the first and last chunk of the range use narrower stores;
+ *     no byte outside the range is written.
+ *   - Asynchronous on the handle's stream. Scratch lives in the handle, grow-only (40 bytes per op): a
+ *     steady-state call does no hipMalloc. entries and payload are 16-byte aligned.
+ *   - WQ_E_INVALID, with nothing launched: a null handle, view, d_cursor; a multi-GPU handle; a null array
+ *     with a non-zero size (d_ops, d_op_ref with n_ops; d_frame_offsets with n_frames; entries with n_entries;
+ *     payload with n_payload_bytes); misaligned entries or payload; n_ops >= 2^31 or n_frames >= 2^32 - 1.
+ * Freeing a dead handle is clearing bit 31 of its entry; the arena is not compacted. */
+typedef struct wq_slab_entry {      /* 64 bytes, indexed by the store's `handle` */
+    uint8_t  uuid[16];
+    double   pos[3];
+    uint32_t world;                 /* id into the table of wq_frames_set_worlds */
+    uint32_t bits;                  /* bit 0 data present, 1 flex present, 2 position present, 31 live */
+    uint64_t off;                   /* data at payload[off .. off+data_len), flex directly behind it */
+    uint32_t data_len, flex_len;
+} wq_slab_entry;
+typedef struct wq_slab_view { wq_slab_entry* entries; uint64_t n_entries; uint8_t* payload; uint64_t n_payload_bytes; } wq_slab_view;
+#define WQ_SLAB_DATA 1u
+#define WQ_SLAB_FLEX 2u
+#define WQ_SLAB_POSITION 4u
+#define WQ_SLAB_LIVE 0x80000000u
+typedef struct wq_slab_counters {
+    uint64_t n_ops, n_creates;
+    uint64_t bytes_stored;          /* the creates' payload bytes: what the cursor advances by */
+    uint64_t bytes_need;            /* cursor + bytes_stored before the call (saturating): the arena size that suffices */
+    uint64_t entries_need;          /* the largest create handle + 1; 0 without a create */
+    uint64_t cursor;                /* *d_cursor after the call */
+    uint32_t overflow;              /* bit 0: the arena, bit 1: the entries; nothing was written */
+    uint32_t error;                 /* bits 0 - 2 above */
+} wq_slab_counters;                 /* 56 bytes */
+int wq_slab_store_device(wq_router* h, const wq_rec_op* d_ops, const wq_rec_op_ref* d_op_ref, size_t n_ops,
+                         const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
+                         const wq_slab_view* view, uint64_t* d_cursor, wq_slab_counters* d_counters /* nullable */);
+
+/* ---- record replies: frames of messages that carry records, built on the device from the slab ----
+ * wq_frames_build_device serializes flat messages. This call serializes messages whose `records` vector is a
+ * row of a CSR of slab handles (what wq_records_read_device returns), with `entities` empty: the RecordReply
+ * of record_read.rs:43-96. The message part is wq_frames_src under every rule it has there; the bytes are
+ * wq_serialize_message's for a message whose records are the row's entries in row order. The host definition
+ * is frames.build_record_frames_np.
+ *   - rec->row_offsets[n_msgs + 1] / handles[n_handles]: the rows, read as the send side reads a CSR: row i is
+ *     the part of [off[i], off[i + 1]) inside [0, n_handles), empty when it descends, and the rows together
+ *     are walked for at most n_handles elements (error bit 6 for any of these).
+ *   - rec->slab: read only. A handle >= n_entries or an entry whose live bit is clear is left out of the
+ *     frame (bit 4). Data at payload[off, off + data_len) or flex at [off + data_len, off + data_len +
+ *     flex_len) that leaves the arena is present and empty (bit 5). An entry's world id outside the table of
+ *     wq_frames_set_worlds gives an empty name (bit 0). The same handle twice gives the record twice. `data`
+ *     is not checked for UTF-8: it came through the decoder.
+ *   - rec->world_bytes / world_off (u64[n_msgs]) / world_len (u32[n_msgs]) / n_world_bytes: optional; when
+ *     given, message i's world name is world_bytes[world_off[i] .. + world_len[i]) and src->world is not
+ *     read. A range that leaves world_bytes is an empty name (bit 0).
+ *   - rec->flags bit 0, WQ_FRAMES_SKIP_EMPTY: a message left without a record is an empty frame of size 0
+ *     (the reference returns before sending, record_read.rs:56-58). Frame i stays message i's.
+ *   - src->sender_uuid NULL is the nil uuid. A frame above 2^30 bytes is empty (bit 3).
+ *   - Capacity, sizing call (d_frames NULL with capacity 0: the arena is then not read), determinism,
+ *     alignment and scratch are wq_frames_build_device's: asynchronous, nothing read back, byte-identical
+ *     every time, a steady-state call does no hipMalloc (scratch: 28 bytes per handle, 36 per message).
+ *     With every row empty and the flag clear the output is wq_frames_build_device's.
+ *   - No lane owns a row or a payload: an element pass over the handles, a segmented scan (the shapes a row
+ *     has seen and the residue its last record left), a place pass, prefix sums of sizes and kept counts, a
+ *     row pass, the scan of the frame sizes and the 1 KiB-tile copy whose composer replays only the records
+ *     that touch its 16-byte chunk.
+ *   - WQ_E_INVALID: what wq_frames_build_device refuses (sender_uuid may be NULL; world may be NULL with
+ *     world_bytes), a null rec, row_offsets NULL with n_msgs, handles NULL with n_handles, n_handles >=
+ *     2^32 - 1, slab entries that are not 16-byte aligned (the arena is read at any alignment), world_off / world_len missing beside world_bytes, unknown flag bits. */
+#define WQ_FRAMES_SKIP_EMPTY 1u
+typedef struct wq_frames_rec_src {
+    const uint32_t* row_offsets;     /* [n_msgs + 1] */
+    const uint32_t* handles;         /* [n_handles] */
+    uint64_t        n_handles;
+    wq_slab_view    slab;            /* read only */
+    const uint8_t*  world_bytes;     /* nullable */
+    const uint64_t* world_off;       /* [n_msgs] */
+    const uint32_t* world_len;       /* [n_msgs] */
+    uint64_t        n_world_bytes;
+    uint32_t        flags, pad_;
+} wq_frames_rec_src;                 /* 96 bytes */
+int wq_frames_build_records_device(wq_router* h, const wq_frames_src* src, const wq_frames_rec_src* rec, size_t n_msgs,
+                                   uint8_t* d_frames, size_t capacity_bytes, uint64_t* d_frame_offsets,
+                                   uint32_t* d_frame_size, wq_frames_counters* d_counters);
+
 /* ---- health of asynchronous ticks ----
  * OR of wq_route_counters.error (error_bits) and of .overflow over every route / global call since
  * the previous wq_route_health on this handle; reading clears them (synchronises the stream). A

@@ -204,6 +204,41 @@ assert REC_OP_REF_DTYPE.itemsize == 32 and RECDISP_DEFER_DTYPE.itemsize == 8 and
 assert RECDISP_COUNTERS_DTYPE.itemsize == 152
 
 
+# ---- record payload slab (wq_slab_store_device) ----
+# struct wq_slab_entry: 64 bytes, indexed by the store's handle
+SLAB_ENTRY_DTYPE = np.dtype([("uuid", np.uint8, (16,)), ("pos", np.float64, (3,)), ("world", np.uint32), ("bits", np.uint32),
+                             ("off", np.uint64), ("data_len", np.uint32), ("flex_len", np.uint32)])
+SLAB_DATA, SLAB_FLEX, SLAB_POSITION, SLAB_LIVE = 1, 2, 4, 0x80000000   # wq_slab_entry.bits
+SLAB_OVERFLOW_ARENA, SLAB_OVERFLOW_ENTRIES = 1, 2                      # wq_slab_counters.overflow
+SLAB_ERROR_FRAME, SLAB_ERROR_DATA, SLAB_ERROR_FLEX = 1, 2, 4           # wq_slab_counters.error
+SLAB_MAX_OPS = 1 << 31
+# struct wq_slab_counters: 56 bytes
+SLAB_COUNTERS_DTYPE = np.dtype([(k, np.uint64) for k in ("n_ops", "n_creates", "bytes_stored", "bytes_need", "entries_need",
+                                                         "cursor")] + [("overflow", np.uint32), ("error", np.uint32)])
+
+
+class SlabView(ctypes.Structure):  # struct wq_slab_view: the caller's device memory
+    _fields_ = [("entries", ctypes.c_void_p), ("n_entries", ctypes.c_uint64), ("payload", ctypes.c_void_p),
+                ("n_payload_bytes", ctypes.c_uint64)]
+
+
+assert SLAB_ENTRY_DTYPE.itemsize == 64 and SLAB_COUNTERS_DTYPE.itemsize == 56 and ctypes.sizeof(SlabView) == 32
+
+
+FRAMES_ERROR_HANDLE, FRAMES_ERROR_ARENA, FRAMES_ERROR_ROWS = 16, 32, 64   # wq_frames_build_records_device: bits 4 - 6
+FRAMES_SKIP_EMPTY = 1                                                   # WQ_FRAMES_SKIP_EMPTY
+
+
+class FramesRecSrc(ctypes.Structure):  # struct wq_frames_rec_src: device pointers
+    _fields_ = [("row_offsets", ctypes.c_void_p), ("handles", ctypes.c_void_p), ("n_handles", ctypes.c_uint64),
+                ("slab", SlabView), ("world_bytes", ctypes.c_void_p), ("world_off", ctypes.c_void_p),
+                ("world_len", ctypes.c_void_p), ("n_world_bytes", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(FramesRecSrc) == 96
+
+
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]
 

@@ -306,6 +306,12 @@ struct wq_router {
     // counts' prefix and the frames' scanned sums; per granule of 64 records the flag words and the two
     // prefixes; the counters
     wq::DevBuf rdp, rdp_ctrl;
+    // record payload slab (wq_slab.hip): per op two elements (data, flex) with their size, source and one
+    // u64 scan entry; the control block between the passes
+    wq::DevBuf slab_ws, slab_ctrl;
+    // record reply builder (wq_reply.hip): per handle the scan state, term, size and two u64 prefixes; per
+    // message the first occurrence of each record shape; sizes and the error word are the frame builder's
+    wq::DevBuf rp_ws;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -453,6 +459,16 @@ void dispatch_release(wq_router* h);
 int launch_records_dispatch(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,
                             wq_recdisp_counters* d_counters);
 void recdispatch_release(wq_router* h);
+// wq_slab.hip: the slab store on device arrays (asynchronous; arguments validated) and its scratch's release.
+int launch_slab_store(wq_router* h, const wq_rec_op* d_ops, const wq_rec_op_ref* d_op_ref, size_t n_ops,
+                      const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames, const wq_slab_view* view,
+                      uint64_t* d_cursor, wq_slab_counters* d_counters);
+void slab_release(wq_router* h);
+// wq_reply.hip: the record reply builder on device arrays (asynchronous; arguments validated) and its release.
+int launch_frames_build_records(wq_router* h, const wq_frames_src* src, const wq_frames_rec_src* rec, size_t n_msgs,
+                                uint8_t* d_frames, size_t capacity_bytes, uint64_t* d_frame_offsets, uint32_t* d_frame_size,
+                                wq_frames_counters* d_counters);
+void reply_release(wq_router* h);
 void ingest_tables(const wq_router* h, DecTables* t);
 bool records_config(const wq_router* h, RecCfg* cfg);
 // wq_records.hip: frees the record store.

@@ -132,6 +132,8 @@ int wq_router_destroy(wq_router* h) {
     ingest_release(h);
     dispatch_release(h);
     recdispatch_release(h);
+    slab_release(h);
+    reply_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -838,6 +840,47 @@ int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_r
         return set_error(h, WQ_E_INVALID, "records_dispatch: an array and its capacity are given together or not at all");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_records_dispatch(h, in, out, d_counters);
+}
+
+int wq_frames_build_records_device(wq_router* h, const wq_frames_src* src, const wq_frames_rec_src* rec, size_t n_msgs,
+                                   uint8_t* d_frames, size_t capacity_bytes, uint64_t* d_frame_offsets,
+                                   uint32_t* d_frame_size, wq_frames_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!src || !rec) return set_error(h, WQ_E_INVALID, "frames_build_records: src or rec is null");
+    if (h->multi) return set_error(h, WQ_E_INVALID, "frames_build_records: a multi-GPU handle has no record path");
+    if (!d_frame_offsets || (n_msgs && (!rec->row_offsets || (!src->world && !rec->world_bytes))) ||
+        (rec->n_handles && !rec->handles) || (rec->slab.n_entries && !rec->slab.entries) ||
+        (rec->slab.n_payload_bytes && !rec->slab.payload && capacity_bytes))
+        return set_error(h, WQ_E_INVALID, "frames_build_records: a null required array");
+    if (rec->world_bytes && n_msgs && (!rec->world_off || !rec->world_len))
+        return set_error(h, WQ_E_INVALID, "frames_build_records: world_bytes without world_off and world_len");
+    if (!src->param != !src->param_offsets || !src->flex != !src->flex_offsets)
+        return set_error(h, WQ_E_INVALID, "frames_build_records: a payload and its offsets are given together or not at all");
+    if (!d_frames && capacity_bytes) return set_error(h, WQ_E_INVALID, "frames_build_records: capacity_bytes without d_frames");
+    if (((uintptr_t)d_frames | (uintptr_t)rec->slab.entries) & 15u)
+        return set_error(h, WQ_E_INVALID, "frames_build_records: d_frames and the slab's entries must be 16-byte aligned");
+    if (rec->flags & ~(uint32_t)WQ_FRAMES_SKIP_EMPTY) return set_error(h, WQ_E_INVALID, "frames_build_records: unknown flag bits");
+    if (n_msgs >= 0xFFFFFFFFull || rec->n_handles >= 0xFFFFFFFFull)
+        return set_error(h, WQ_E_INVALID, "frames_build_records: n_msgs and n_handles must be < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_frames_build_records(h, src, rec, n_msgs, d_frames, capacity_bytes, d_frame_offsets, d_frame_size, d_counters);
+}
+
+int wq_slab_store_device(wq_router* h, const wq_rec_op* d_ops, const wq_rec_op_ref* d_op_ref, size_t n_ops,
+                         const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
+                         const wq_slab_view* view, uint64_t* d_cursor, wq_slab_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!view || !d_cursor) return set_error(h, WQ_E_INVALID, "slab_store: view or d_cursor is null");
+    if (h->multi) return set_error(h, WQ_E_INVALID, "slab_store: a multi-GPU handle has no record path");
+    if ((n_ops && (!d_ops || !d_op_ref)) || (n_frames && !d_frame_offsets) || (view->n_entries && !view->entries) ||
+        (view->n_payload_bytes && !view->payload))
+        return set_error(h, WQ_E_INVALID, "slab_store: a null array with a non-zero size");
+    if (((uintptr_t)view->entries | (uintptr_t)view->payload) & 15u)
+        return set_error(h, WQ_E_INVALID, "slab_store: entries and payload must be 16-byte aligned");
+    if (n_ops >= (1ull << 31) || n_frames >= 0xFFFFFFFFull)
+        return set_error(h, WQ_E_INVALID, "slab_store: n_ops must be < 2^31 and n_frames < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_slab_store(h, d_ops, d_op_ref, n_ops, d_frames, d_frame_offsets, n_frames, view, d_cursor, d_counters);
 }
 
 int wq_debug_set_ingest_list(wq_router* h, int64_t entries) {

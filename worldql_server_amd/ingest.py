@@ -832,6 +832,56 @@ class IngestTick:
         got.update(counters=cnt, runs=runs)
         return got
 
+    def slab_store(self, frames, offsets, slab, n_ops: int) -> dict:
+        """The payloads of the tick's created records into a records.DeviceRecordSlab, on the ops and
+        references records_dispatch() left and the frames / offsets decode() took. n_ops: the accepted ops,
+        n_creates + n_deletes of the record dispatch's counters (the rows behind them are an earlier tick's).
+        Returns the slab's counters of the call that fitted (DeviceRecordSlab.store grows and retries)."""
+        return slab.store(self.r_out.ops, self.r_out.op_ref, int(n_ops), frames.data_ptr() if frames.numel() else 0,
+                          offsets.data_ptr(), self.n)
+
+    INS_RECORD_REPLY = 12   # codec.INSTRUCTION_NAMES
+
+    def build_record_frames(self, lo: int, hi: int, frames, offsets, row_offsets, handles, n_handles: int, slab_view,
+                            flags: int = abi.FRAMES_SKIP_EMPTY):
+        """The RecordReply frames of the query rows [lo, hi) records_dispatch() left, through
+        Router.build_record_frames_device: row_offsets (i32[hi - lo + 1]) / handles (i32, None without any) are
+        the device tensors wq_records_read_device filled for those rows, slab_view the abi.SlabView of the
+        payload slab, frames / offsets the tensors decode() took. Every reply is Message { RecordReply, the
+        query's world name as its frame held it (taken from the frames on the device), the row's records, the
+        rest default }. A sizing call, one read of its counters, then the build. Returns (frames u8, sizes
+        i32[hi - lo], recipients i32[hi - lo]: the decode's `sender` of each query) as device tensors;
+        ValueError when the build reports an error bit."""
+        import torch
+        n, dev = hi - lo, self.device
+        # where each query's world name lies, and who asked (torch's stream; waited for below)
+        q_src = self.rbuf["q_src"][4 * lo:4 * hi].view(torch.int32).to(torch.int64)
+        msg = self.buf["msg"][:self.n * 72].view(self.n, 72)[q_src]
+        w_off = (offsets.view(torch.int64)[q_src] + msg[:, 48:52].contiguous().view(torch.int32).view(-1).to(torch.int64)).contiguous()
+        w_len = msg[:, 52:56].contiguous().view(torch.int32).view(-1).contiguous()
+        recipients = self.buf["sender"][:self.n * 4].view(torch.int32)[q_src].contiguous()
+        src = abi.FramesSrc(instruction_all=self.INS_RECORD_REPLY)
+        rec = abi.FramesRecSrc(row_offsets=row_offsets.data_ptr(), handles=handles.data_ptr() if handles is not None and n_handles else None,
+                               n_handles=n_handles, slab=slab_view, world_bytes=frames.data_ptr() if frames.numel() else None,
+                               world_off=w_off.data_ptr(), world_len=w_len.data_ptr(), n_world_bytes=frames.numel(), flags=flags)
+        if not frames.numel():
+            zero_world = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            rec.world_bytes, src.world = None, zero_world.data_ptr()
+        fo = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        sizes = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        cnt = torch.empty(abi.FRAMES_COUNTERS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        self.router.build_record_frames_device(src, rec, n, None, 0, fo.data_ptr(), None, cnt.data_ptr())
+        torch.cuda.synchronize()
+        nbytes = int(cnt.cpu().numpy().view(abi.FRAMES_COUNTERS_DTYPE)[0]["bytes_need"])
+        out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        self.router.build_record_frames_device(src, rec, n, out.data_ptr(), nbytes, fo.data_ptr(), sizes.data_ptr(), cnt.data_ptr())
+        torch.cuda.synchronize()
+        c = cnt.cpu().numpy().view(abi.FRAMES_COUNTERS_DTYPE)[0]
+        if int(c["error"]) or int(c["overflow"]):
+            raise ValueError(f"record frames: error {int(c['error']):#x}, overflow {int(c['overflow'])}")
+        return out[:nbytes], sizes, recipients
+
     def read_msg_rows(self, frames_idx) -> np.ndarray:
         """The decoder's msg structs of the given frames (after a read that waited for the device)."""
         import torch

@@ -6,6 +6,8 @@ handle_record_read (processing/record_read.rs) restated, with what the reference
 fixed as the header says. `GpuRecordStore` is the ctypes binding of the wq_records_* calls and
 `RecordProcessor` the host side of the three instructions around it. `DeviceRecordProcessor` is the same
 with the per-record work on the device (wq_records_dispatch_device through ingest.IngestTick).
+`slab_store_np` is the definition of wq_slab_store_device (csrc/wq_slab.hip), which keeps the created
+records' payloads in device memory, and `DeviceRecordSlab` the torch-side owner of that slab.
 """
 from __future__ import annotations
 
@@ -777,3 +779,316 @@ class DeviceRecordProcessor:
         for hd in self.store.drain_dead():
             self.slab[int(hd)] = None
             self.free.append(int(hd))
+
+
+    # ---- the same tick with the slab and the replies on the device ----
+
+    def process_frames(self, data, offsets, now_us: int, d_frames=None, d_offsets=None) -> dict:
+        """`process`'s tick with the payloads in a DeviceRecordSlab (`self.dslab`, filled by
+        wq_slab_store_device from the frames where they lie) and the replies built by
+        wq_frames_build_records_device: nothing per record happens on the host. Returns a dict of device
+        tensors: frames (u8), offsets (i64[n + 1]), sizes (i32[n]) and recipients (i32[n]: the decode's
+        `sender` of each answered query, -1 = 0xFFFFFFFF for a sender the table lacks), one frame per READ
+        query in run order; a query that found nothing has a frame of size 0 (WQ_FRAMES_SKIP_EMPTY) and is
+        sent to nobody. A reply is Message { RecordReply, the query's world name as its frame held it, the
+        records, the rest default }, the bytes of the host serializer. Read back: the dispatch's counters and
+        runs, the slab's and the builder's counters, the reads' totals and the store's dead list, as `process`
+        reads for control. The handles are this path's own (`process` and `process_frames` do not share a
+        slab: use one of them on a store). Deferred creates and deletes (a world name outside the router's
+        table) go through the host after the tick, the payload by DeviceRecordSlab.put_host; a deferred
+        read raises NotImplementedError: answer it with `process`."""
+        import torch
+        from . import ingest
+        tick, dev = self.tick, self.tick.device
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if d_frames is None:
+            d_frames = torch.from_numpy(data.copy() if len(data) else np.zeros(1, np.uint8)).to(dev)[:len(data)]
+            d_offsets = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
+        if not hasattr(self, "dslab"):
+            self.dslab, self.d_free, self.d_next = DeviceRecordSlab(self.router, dev), [], 0
+        tick.decode(d_frames, d_offsets).dispatch()
+        tick.records_dispatch(d_frames, d_offsets, now_us, free_handles=self.d_free[::-1], handle_next=self.d_next)
+        cnt, runs = tick.read_records_ctrl()
+        self.last_counters = cnt
+        if cnt["overflow"] or cnt["error"]:
+            raise ValueError(f"records dispatch: overflow {cnt['overflow']:#x}, error {cnt['error']:#x}")
+        if cnt["n_read_deferred"]:
+            raise NotImplementedError("process_frames: a read of a world outside the router's table; use process")
+        n_ops = cnt["n_creates"] + cnt["n_deletes"]
+        if cnt["n_creates"]:
+            taken = min(cnt["n_creates"], len(self.d_free))
+            del self.d_free[len(self.d_free) - taken:]
+            self.d_next += cnt["n_creates"] - taken
+            got = tick.slab_store(d_frames, d_offsets, self.dslab, n_ops)
+            if got["error"]:
+                raise ValueError(f"slab store: error {got['error']:#x}")
+        out, o = [], tick.r_out
+        for a, b in zip(runs[:-1], runs[1:]):
+            if a["kind"] == abi.RRUN_APPLY:
+                lo, hi = int(a["op_begin"]), int(b["op_begin"])
+                self.store.apply_device(o.ops + 64 * lo, hi - lo)
+                continue
+            out += self._read_frames(int(a["q_begin"]), int(b["q_begin"]), d_frames, d_offsets)
+        self._free_dead_device()
+        if cnt["n_deferred_records"]:
+            self._deferred_records(cnt, data, offsets, now_us)
+        i32 = lambda: torch.zeros(0, dtype=torch.int32, device=dev)   # noqa: E731
+        frames = torch.cat([x[0] for x in out]) if out else torch.zeros(0, dtype=torch.uint8, device=dev)
+        sizes = torch.cat([x[1] for x in out]) if out else i32()
+        off = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=dev)
+        off[1:] = torch.cumsum(sizes.to(torch.int64), 0)
+        return dict(frames=frames, offsets=off, sizes=sizes, recipients=torch.cat([x[2] for x in out]) if out else i32())
+
+    def _read_frames(self, lo: int, hi: int, d_frames, d_offsets) -> list:
+        """One read run on the device: rows [lo, hi) of the query arrays -> [(frames, sizes, recipients)]."""
+        import torch
+        tick, o, n, dev = self.tick, self.tick.r_out, hi - lo, self.tick.device
+        d_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        args = (n, o.q_world + 4 * lo, o.q_pos + 24 * lo, o.q_after + 8 * lo)
+        try:
+            sizing = self.store.read_device(*args, False, d_off.data_ptr(), 0, 0, 0)
+            need = sizing["returned"]
+            self.sizing_rejected += sizing["rejected"]
+            d_h = torch.empty(max(need, 1), dtype=torch.int32, device=dev)
+            d_ts = torch.empty(max(need, 1), dtype=torch.int64, device=dev)
+            self.store.read_device(*args, self.dedupe, d_off.data_ptr(), d_h.data_ptr() if need else 0,
+                                   d_ts.data_ptr() if need else 0, need)
+        except ReadTooLarge:
+            if n == 1:
+                raise
+            return self._read_frames(lo, lo + n // 2, d_frames, d_offsets) + self._read_frames(lo + n // 2, hi, d_frames, d_offsets)
+        return [tick.build_record_frames(lo, hi, d_frames, d_offsets, d_off, d_h if need else None, need, self.dslab.view())]
+
+    def _free_dead_device(self):
+        dead = self.store.drain_dead()
+        if len(dead):
+            self.dslab.free(dead)
+            self.d_free.extend(int(h) for h in dead)
+
+    def _deferred_records(self, cnt, data, offsets, now_us: int):
+        """The deferred creates and deletes on the host, after the tick: the names are interned and added to the
+        router's table, the ops applied through the host form, the created payloads put into the device slab."""
+        from . import ingest
+        off = [int(v) for v in offsets]
+        frame = lambda f: data[off[f]:off[f + 1]].tobytes()   # noqa: E731
+        pairs = self.tick.read_records_rows("defer", 0, cnt["n_deferred_records"])
+        self.deferred += len(pairs)
+        idx = sorted({int(p["frame"]) for p in pairs})
+        rows = dict(zip(idx, self.tick.read_msg_rows(idx)))
+        ops, puts = [], []
+        for p in pairs:
+            ev = ingest.deferred_event(frame(int(p["frame"])), rows[int(p["frame"])], int(p["record"]))
+            kind = CREATE if ev["instruction"] == "RecordCreate" else DELETE
+            for r in ev["records"]:
+                try:
+                    world = self.fallback.worlds.intern(sanitize_world_name(r["world_name"]))
+                except SanitizeError:
+                    continue
+                if r.get("position") is None or not position_packable(self.store.sizes, world, r["position"]):
+                    continue
+                handle = 0
+                if kind == CREATE:
+                    handle = self.d_free.pop() if self.d_free else self.d_next
+                    self.d_next += handle == self.d_next
+                    puts.append((handle, r, world))
+                ops.append((kind, world, tuple(r["position"]), r["uuid"][0], r["uuid"][1], now_us, handle, 0))
+        if len(self.fallback.worlds) > len(self.names):
+            self.names = [self.fallback.worlds.name(w) for w in range(len(self.fallback.worlds))]
+            self.router.set_worlds(self.names)
+        for handle, r, world in puts:
+            self.dslab.put_host(handle, r, world)
+        if ops:
+            self.store.apply(np.array(ops, dtype=REC_OP_DTYPE))
+            self._free_dead_device()
+
+
+# ---- the record payload slab (wq_slab_store_device, csrc/wq_slab.hip) ----
+
+def slab_store_np(ops, op_ref, frames, offsets, entries, payload, cursor: int):
+    """The definition of wq_slab_store_device: the header's rules in plain Python. ops (REC_OP_DTYPE) and
+    op_ref (abi.REC_OP_REF_DTYPE) as the record dispatch wrote them, frames u8 / offsets u64[n_frames + 1]
+    the tick's frames, entries (abi.SLAB_ENTRY_DTYPE) and payload (u8) the slab, cursor the arena's fill.
+    Returns (entries, payload, cursor, counters): copies with the call applied, or unchanged after an
+    overflow, and the counters as a dict with abi.SLAB_COUNTERS_DTYPE's fields."""
+    ops = np.ascontiguousarray(ops, dtype=REC_OP_DTYPE)
+    op_ref = np.ascontiguousarray(op_ref, dtype=abi.REC_OP_REF_DTYPE)
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    fo = [int(v) for v in np.ascontiguousarray(offsets, dtype=np.uint64)]
+    n_frames = max(len(fo) - 1, 0)
+    n_frame_bytes = fo[n_frames] if n_frames else 0
+    entries, payload = np.array(entries, dtype=abi.SLAB_ENTRY_DTYPE), np.array(payload, dtype=np.uint8)
+    error, at, need, plan = 0, int(cursor), 0, []
+    for op, ref in zip(ops, op_ref):
+        if int(op["kind"]) != CREATE:
+            continue
+        bits = int(ref["bits"]) & 3
+        want = [(int(ref["data_off"]), int(ref["data_len"]) if bits & 1 else 0),
+                (int(ref["flex_off"]), int(ref["flex_len"]) if bits & 2 else 0)]
+        parts = [b"", b""]
+        if want[0][1] or want[1][1]:   # nothing to copy: the frame is not looked at
+            f = int(ref["frame"])
+            ok = f < n_frames and fo[f] <= fo[f + 1] <= n_frame_bytes
+            if not ok:
+                error |= abi.SLAB_ERROR_FRAME
+            else:
+                for k, (o, ln) in enumerate(want):
+                    if not ln:
+                        continue
+                    if o + ln > fo[f + 1] - fo[f]:
+                        error |= abi.SLAB_ERROR_FLEX if k else abi.SLAB_ERROR_DATA
+                        continue
+                    parts[k] = frames[fo[f] + o:fo[f] + o + ln].tobytes()
+        need = max(need, int(op["handle"]) + 1)
+        plan.append((op, bits, at, parts))
+        at += len(parts[0]) + len(parts[1])
+    total = at - int(cursor)
+    overflow = (abi.SLAB_OVERFLOW_ARENA if int(cursor) > len(payload) or total > len(payload) - int(cursor) else 0) | \
+               (abi.SLAB_OVERFLOW_ENTRIES if need > len(entries) else 0)
+    if not overflow:
+        for op, bits, off, parts in plan:
+            e = entries[int(op["handle"])]
+            e["uuid"] = np.frombuffer(int(op["uuid_hi"]).to_bytes(8, "big") + int(op["uuid_lo"]).to_bytes(8, "big"), np.uint8)
+            e["pos"], e["world"] = op["pos"], op["world"]
+            e["bits"] = bits | abi.SLAB_POSITION | abi.SLAB_LIVE
+            e["off"], e["data_len"], e["flex_len"] = off, len(parts[0]), len(parts[1])
+            blob = parts[0] + parts[1]
+            payload[off:off + len(blob)] = np.frombuffer(blob, np.uint8)
+    counters = dict(n_ops=len(ops), n_creates=len(plan), bytes_stored=total, bytes_need=min(int(cursor) + total, 2**64 - 1),
+                    entries_need=need, cursor=int(cursor) if overflow else at, overflow=overflow, error=error)
+    return entries, payload, counters["cursor"], counters
+
+
+def slab_counters(raw) -> dict:
+    """abi.SLAB_COUNTERS_DTYPE bytes as slab_store_np's counters dict."""
+    c = np.frombuffer(bytes(raw), dtype=abi.SLAB_COUNTERS_DTYPE)[0]
+    return {k: int(c[k]) for k in abi.SLAB_COUNTERS_DTYPE.names}
+
+
+class DeviceRecordSlab:
+    """The payload slab in device memory: torch tensors for the entries (abi.SLAB_ENTRY_DTYPE, indexed by
+    the store's handle) and the byte arena, and the arena's fill as a device word. `store` is
+    Router.slab_store_device with grow-and-retry: the one read-back is the call's counters. `free` clears
+    the live bit of dead handles and adds their payload bytes to the dead count; the arena is never
+    compacted, `dead_bytes` says how much of it nothing refers to any more. `put_host` stores one record
+    the host holds (what the host fallback creates from deferred records)."""
+
+    def __init__(self, router, device, n_entries: int = 1024, n_payload_bytes: int = 1 << 16):
+        import torch
+        self.router, self.device = router, device
+        # zeros, and waited for: the calls run on the handle's stream, not torch's
+        self.entries = torch.zeros(max(n_entries, 1), 8, dtype=torch.int64, device=device)
+        self.payload = torch.zeros(max(n_payload_bytes, 16), dtype=torch.uint8, device=device)
+        self.ctrl = torch.zeros(8 + abi.SLAB_COUNTERS_DTYPE.itemsize, dtype=torch.uint8, device=device)  # cursor, counters
+        self.dead = torch.zeros(1, dtype=torch.int64, device=device)
+        self.cursor = 0          # the host's mirror of the device word, as of the last store
+        self.grows = 0
+        torch.cuda.synchronize()
+
+    @property
+    def n_entries(self) -> int:
+        return self.entries.shape[0]
+
+    @property
+    def n_payload_bytes(self) -> int:
+        return self.payload.numel()
+
+    @property
+    def dead_bytes(self) -> int:
+        """Arena bytes of freed entries (one read-back)."""
+        return int(self.dead.item())
+
+    def view(self) -> "abi.SlabView":
+        return abi.SlabView(entries=self.entries.data_ptr(), n_entries=self.n_entries, payload=self.payload.data_ptr(),
+                            n_payload_bytes=self.n_payload_bytes)
+
+    def _grow(self, n_entries: int, n_bytes: int) -> None:
+        import torch
+        if n_entries <= self.n_entries and n_bytes <= self.n_payload_bytes:
+            return
+        torch.cuda.synchronize()
+        if n_entries > self.n_entries:
+            new = torch.zeros(max(n_entries, 2 * self.n_entries), 8, dtype=torch.int64, device=self.device)
+            new[:self.n_entries] = self.entries
+            self.entries = new
+        if n_bytes > self.n_payload_bytes:
+            new = torch.zeros(max(n_bytes, 2 * self.n_payload_bytes), dtype=torch.uint8, device=self.device)
+            new[:self.cursor] = self.payload[:self.cursor]
+            self.payload = new
+        self.grows += 1
+        torch.cuda.synchronize()
+
+    def store(self, ops_ptr: int, op_ref_ptr: int, n_ops: int, frames_ptr: int, frame_offsets_ptr: int, n_frames: int) -> dict:
+        """One wq_slab_store_device call on device arrays; after an overflow the slab grows to what the
+        counters ask for and the call is repeated once. Returns the counters of the call that fitted."""
+        import torch
+        for _ in range(2):
+            self.router.slab_store_device(ops_ptr, op_ref_ptr, n_ops, frames_ptr, frame_offsets_ptr, n_frames, self.view(),
+                                          self.ctrl.data_ptr(), self.ctrl.data_ptr() + 8)
+            torch.cuda.synchronize()
+            cnt = slab_counters(self.ctrl[8:].cpu().numpy())
+            if not cnt["overflow"]:
+                self.cursor = cnt["cursor"]
+                return cnt
+            self._grow(cnt["entries_need"], cnt["bytes_need"])
+        raise RuntimeError(f"slab store: overflow {cnt['overflow']:#x} after growing")
+
+    def free(self, handles) -> None:
+        """Clears the live bit of the given handles' entries (a torch index write); their payload bytes count
+        as dead. Handles that are not live, or past the entries, change nothing."""
+        import torch
+        hd = np.unique(np.asarray(handles, dtype=np.int64))
+        hd = hd[hd < self.n_entries]
+        if not len(hd):
+            return
+        idx = torch.from_numpy(hd).to(self.device)
+        w5, w7 = self.entries[idx, 5], self.entries[idx, 7]
+        live = w5 < 0   # bit 31 of `bits` is the word's sign
+        self.dead += torch.where(live, (w7 & 0xFFFFFFFF) + ((w7 >> 32) & 0xFFFFFFFF), torch.zeros_like(w7)).sum()
+        self.entries[idx, 5] = w5 & 0x7FFFFFFFFFFFFFFF
+        torch.cuda.synchronize()
+
+    def put_host(self, handle: int, record: dict, world: int) -> None:
+        """One record from the host under `handle`: {"uuid": (hi, lo), "position", "data" (str or None),
+        "flex" (bytes or None)}; world: its id in the router's table. Per-record host work (three small uploads
+        and a device synchronise a record): it is for the few records the host fallback creates from deferred
+        entries, not for a tick's creates."""
+        import torch
+        data = None if record.get("data") is None else record["data"].encode("utf-8")
+        flex = None if record.get("flex") is None else bytes(record["flex"])
+        blob = (data or b"") + (flex or b"")
+        if handle >= self.n_entries or self.cursor + len(blob) > self.n_payload_bytes:
+            self._grow(handle + 1, self.cursor + len(blob))
+        e = np.zeros(1, dtype=abi.SLAB_ENTRY_DTYPE)
+        e["uuid"][0] = np.frombuffer(int(record["uuid"][0]).to_bytes(8, "big") + int(record["uuid"][1]).to_bytes(8, "big"), np.uint8)
+        e["pos"][0], e["world"] = record["position"], world
+        e["bits"] = (abi.SLAB_DATA if data is not None else 0) | (abi.SLAB_FLEX if flex is not None else 0) | \
+            abi.SLAB_POSITION | abi.SLAB_LIVE
+        e["off"], e["data_len"], e["flex_len"] = self.cursor, len(data or b""), len(flex or b"")
+        self.entries[handle] = torch.from_numpy(e.view(np.int64).copy()).to(self.device)
+        if blob:
+            self.payload[self.cursor:self.cursor + len(blob)] = torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to(self.device)
+        self.cursor += len(blob)
+        self.ctrl[:8] = torch.from_numpy(np.array([self.cursor], np.uint64).view(np.uint8).copy()).to(self.device)
+        torch.cuda.synchronize()
+
+    def read(self):
+        """(entries as abi.SLAB_ENTRY_DTYPE, the arena's bytes below the cursor): synchronizes; for tests."""
+        import torch
+        torch.cuda.synchronize()
+        return (self.entries.cpu().numpy().reshape(-1).view(abi.SLAB_ENTRY_DTYPE).copy(),
+                self.payload[:self.cursor].cpu().numpy().copy())
+
+    def get(self, handle: int, raw_data: bool = False):
+        """The record under `handle` as put_host takes it, plus "world"; None when it is not live (reads back).
+        raw_data: `data` as the bytes the arena holds, not decoded."""
+        e = self.entries[handle].cpu().numpy().view(abi.SLAB_ENTRY_DTYPE)[0]
+        if not int(e["bits"]) & abi.SLAB_LIVE:
+            return None
+        off, dl, fl = int(e["off"]), int(e["data_len"]), int(e["flex_len"])
+        raw = self.payload[off:off + dl + fl].cpu().numpy().tobytes()
+        u = bytes(e["uuid"])
+        return {"uuid": (int.from_bytes(u[:8], "big"), int.from_bytes(u[8:], "big")), "world": int(e["world"]),
+                "position": tuple(float(c) for c in e["pos"]),
+                "data": (raw[:dl] if raw_data else raw[:dl].decode("utf-8")) if int(e["bits"]) & abi.SLAB_DATA else None,
+                "flex": raw[dl:] if int(e["bits"]) & abi.SLAB_FLEX else None}

@@ -93,6 +93,8 @@ def load_library(build_if_missing: bool = True):
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
         "wq_records_dispatch_device": ([vp, ctypes.POINTER(abi.RecDispatchIn), ctypes.POINTER(abi.RecDispatchOut), vp], i32),
+        "wq_frames_build_records_device": ([vp, ctypes.POINTER(abi.FramesSrc), ctypes.POINTER(abi.FramesRecSrc), sz, vp, sz, vp, vp, vp], i32),
+        "wq_slab_store_device": ([vp, vp, vp, sz, vp, vp, sz, ctypes.POINTER(abi.SlabView), vp, vp], i32),
         "wq_records_open": ([vp, u16, u16, u16, u32], i32),
         "wq_records_close": ([vp], i32),
         "wq_records_apply": ([vp, vp, sz, vp], i32),
@@ -528,6 +530,32 @@ class Router:
         self._check(self.lib.wq_records_dispatch_device(self.h, ctypes.byref(src) if src is not None else None,
                                                         ctypes.byref(out) if out is not None else None,
                                                         counters_ptr or None))
+
+    def build_record_frames_device(self, src: "abi.FramesSrc", rec: "abi.FramesRecSrc", n_msgs: int, frames_ptr: int | None,
+                                   capacity_bytes: int, frame_offsets_ptr: int, frame_size_ptr: int | None = None,
+                                   counters_ptr: int | None = None) -> None:
+        """wq_frames_build_records_device: build_frames_device for messages that carry records. rec
+        (abi.FramesRecSrc) holds a CSR of slab handles (row_offsets u32[n_msgs + 1], handles), the slab
+        (abi.SlabView, read only), optional per-message world names as bytes and the flags
+        (abi.FRAMES_SKIP_EMPTY). Output, capacity, sizing call and counters as build_frames_device. Asynchronous
+        on the handle's stream. Host definition: frames.build_record_frames_np."""
+        self._check(self.lib.wq_frames_build_records_device(self.h, ctypes.byref(src), ctypes.byref(rec), n_msgs,
+                                                            frames_ptr or None, capacity_bytes, frame_offsets_ptr,
+                                                            frame_size_ptr or None, counters_ptr or None))
+
+    def slab_store_device(self, ops_ptr: int | None, op_ref_ptr: int | None, n_ops: int, frames_ptr: int | None,
+                          frame_offsets_ptr: int | None, n_frames: int, view: "abi.SlabView", cursor_ptr: int,
+                          counters_ptr: int | None = None) -> None:
+        """wq_slab_store_device: the payloads of the creates among n_ops ops (wq_rec_op / wq_rec_op_ref as
+        records_dispatch_device wrote them) copied from the tick's frames into the caller's slab (abi.SlabView:
+        entries indexed by handle and a byte arena, device memory), placed from the device word at cursor_ptr,
+        which the call advances. All or nothing: an arena or entry array that is too small leaves slab and
+        cursor as they were and says so in the counters (abi.SLAB_COUNTERS_DTYPE, where counters_ptr points).
+        Asynchronous on the handle's stream; nothing is read back. Host definition: records.slab_store_np."""
+        self._check(self.lib.wq_slab_store_device(self.h, ops_ptr or None, op_ref_ptr or None, n_ops, frames_ptr or None,
+                                                  frame_offsets_ptr or None, n_frames,
+                                                  ctypes.byref(view) if view is not None else None, cursor_ptr or None,
+                                                  counters_ptr or None))
 
     def set_ingest_list(self, entries: int) -> None:
         """wq_debug_set_ingest_list: a test hook, the long-string work list's capacity (0: none; negative:
