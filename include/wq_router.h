@@ -1658,7 +1658,7 @@ int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_r
  *   - WQ_E_INVALID, with nothing launched: a null handle, view, d_cursor; a multi-GPU handle; a null array
  *     with a non-zero size (d_ops, d_op_ref with n_ops; d_frame_offsets with n_frames; entries with n_entries;
  *     payload with n_payload_bytes); misaligned entries or payload; n_ops >= 2^31 or n_frames >= 2^32 - 1.
- * Freeing a dead handle is clearing bit 31 of its entry; the arena is not compacted. */
+ * Freeing a dead handle is clearing bit 31 of its entry; wq_slab_compact_device (below) gets its bytes back. */
 typedef struct wq_slab_entry {      /* 64 bytes, indexed by the store's `handle` */
     uint8_t  uuid[16];
     double   pos[3];
@@ -1684,6 +1684,54 @@ typedef struct wq_slab_counters {
 int wq_slab_store_device(wq_router* h, const wq_rec_op* d_ops, const wq_rec_op_ref* d_op_ref, size_t n_ops,
                          const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
                          const wq_slab_view* view, uint64_t* d_cursor, wq_slab_counters* d_counters /* nullable */);
+
+/* ---- slab compaction: a slab rewritten in its canonical form ----
+ * The store appends and a free only clears a live bit, so an arena fills with bytes nothing refers to. This
+ * call writes the slab `src` into the slab `dst` in one canonical form: the live payloads back to back in
+ * handle order, every other entry zero. Into a second arena that is compaction (the caller swaps), into a
+ * buffer the host reads back it is an export, from an uploaded file into a fresh slab it is a validated
+ * import. Handles keep their numbers: the record store's rows hold them. The host definition is
+ * records.slab_compact_np.
+ *
+ *   - Handle i < src->n_entries is kept when bit 31 (live) of its entry is set. A kept entry goes to
+ *     dst->entries[i] with every field as it was except `off`; its data_len + flex_len bytes go to
+ *     dst->payload[off' ..), data first and flex directly behind it.
+ *   - Every other entry of dst is 64 zero bytes: dead handles, and handles at or above src->n_entries when
+ *     dst is longer. All dst->n_entries entries are written, so two slabs that hold the same live records
+ *     compact to the same bytes whatever their histories.
+ *   - Placement: off' is the u64 exclusive scan of the kept entries' data_len + flex_len in ascending handle
+ *     order, from 0, without padding. *d_dst_cursor becomes the total.
+ *   - All or nothing. Overflow bit 0: the total exceeds dst->n_payload_bytes. Bit 1: the highest live handle
+ *     + 1 exceeds dst->n_entries. After either no byte of dst is written and *d_dst_cursor stays; the
+ *     counters' bytes_live and entries_need are the sizes that suffice. dst may have fewer entries than src
+ *     (trailing dead handles are trimmed). A dst with n_payload_bytes == 0 and a null payload is the sizing
+ *     call.
+ *   - Hostile entries (never a fault). A live entry whose range [off, off + data_len + flex_len) leaves
+ *     src->n_payload_bytes (checked in u64: an `off` near 2^64 does not wrap) stays live and keeps its
+ *     presence bits, both lengths become 0 and error bit 0 is set: the reply builder's bit-5 rule. Two live
+ *     entries that share or overlap a source range are each copied; that is no error. world and pos are
+ *     carried as they are. A total past 2^64 - 1 saturates, which is an arena overflow.
+ *   - No byte of dst->payload at or beyond the total is written, and no input is written.
+ *   - The passes: flags and sizes over the entries as 16-byte chunks, four lanes per entry; one scan of
+ *     (live, size); a one-lane decision; the entries, again four lanes each; the copy over the destination's
+ *     bytes like wq_slab_store_device's, whose elements are the live entries alone, so a run of dead handles
+ *     costs the copy nothing. Placement comes from the scan: the result is the same bytes every time.
+ *   - Asynchronous on the handle's stream. Scratch lives in the handle, grow-only (40 bytes per source
+ *     entry); nothing is read back.
+ *   - WQ_E_INVALID, with nothing launched: a null handle, src, dst or d_dst_cursor; a multi-GPU handle; a null
+ *     array with a non-zero size; entries, or dst's payload, that are not 16-byte aligned (src's arena is only
+ *     read, at any alignment, as the reply builder reads it); n_entries >= 2^32 - 1 on either side; src and dst entry arrays that overlap, or payload arenas that overlap (the call is out of
+ *     place). */
+typedef struct wq_slab_compact_counters {
+    uint64_t n_entries;             /* src->n_entries */
+    uint64_t n_live;                /* kept entries */
+    uint64_t bytes_live;            /* their payload bytes: the total, and the arena size that suffices */
+    uint64_t entries_need;          /* the highest live handle + 1; 0 without a live entry */
+    uint32_t overflow;              /* bit 0: the arena, bit 1: the entries; nothing was written */
+    uint32_t error;                 /* bit 0 above */
+} wq_slab_compact_counters;         /* 40 bytes */
+int wq_slab_compact_device(wq_router* h, const wq_slab_view* src, const wq_slab_view* dst, uint64_t* d_dst_cursor,
+                           wq_slab_compact_counters* d_counters /* nullable */);
 
 /* ---- record replies: frames of messages that carry records, built on the device from the slab ----
  * wq_frames_build_device serializes flat messages. This call serializes messages whose `records` vector is a

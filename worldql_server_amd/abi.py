@@ -224,6 +224,14 @@ class SlabView(ctypes.Structure):  # struct wq_slab_view: the caller's device me
 
 assert SLAB_ENTRY_DTYPE.itemsize == 64 and SLAB_COUNTERS_DTYPE.itemsize == 56 and ctypes.sizeof(SlabView) == 32
 
+# ---- slab compaction (wq_slab_compact_device) ----
+# struct wq_slab_compact_counters: 40 bytes; overflow takes SLAB_OVERFLOW_ARENA / SLAB_OVERFLOW_ENTRIES
+SLAB_COMPACT_COUNTERS_DTYPE = np.dtype([(k, np.uint64) for k in ("n_entries", "n_live", "bytes_live", "entries_need")] +
+                                       [("overflow", np.uint32), ("error", np.uint32)])
+SLAB_COMPACT_ERROR_RANGE = 1          # wq_slab_compact_counters.error: a live entry whose range leaves the source arena
+SLAB_COMPACT_MAX_ENTRIES = 0xFFFFFFFF
+assert SLAB_COMPACT_COUNTERS_DTYPE.itemsize == 40
+
 
 FRAMES_ERROR_HANDLE, FRAMES_ERROR_ARENA, FRAMES_ERROR_ROWS = 16, 32, 64   # wq_frames_build_records_device: bits 4 - 6
 FRAMES_SKIP_EMPTY = 1                                                   # WQ_FRAMES_SKIP_EMPTY

@@ -309,6 +309,9 @@ struct wq_router {
     // record payload slab (wq_slab.hip): per op two elements (data, flex) with their size, source and one
     // u64 scan entry; the control block between the passes
     wq::DevBuf slab_ws, slab_ctrl;
+    // slab compaction (wq_slab_compact.hip): per source entry its term, the scan's pair and one element of the
+    // dense list of live entries; the control block between the passes
+    wq::DevBuf cmp_ws, cmp_ctrl;
     // record reply builder (wq_reply.hip): per handle the scan state, term, size and two u64 prefixes; per
     // message the first occurrence of each record shape; sizes and the error word are the frame builder's
     wq::DevBuf rp_ws;
@@ -464,6 +467,10 @@ int launch_slab_store(wq_router* h, const wq_rec_op* d_ops, const wq_rec_op_ref*
                       const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames, const wq_slab_view* view,
                       uint64_t* d_cursor, wq_slab_counters* d_counters);
 void slab_release(wq_router* h);
+// wq_slab_compact.hip: the slab's compaction on device arrays (asynchronous; arguments validated) and its release.
+int launch_slab_compact(wq_router* h, const wq_slab_view* src, const wq_slab_view* dst, uint64_t* d_dst_cursor,
+                        wq_slab_compact_counters* d_counters);
+void slab_compact_release(wq_router* h);
 // wq_reply.hip: the record reply builder on device arrays (asynchronous; arguments validated) and its release.
 int launch_frames_build_records(wq_router* h, const wq_frames_src* src, const wq_frames_rec_src* rec, size_t n_msgs,
                                 uint8_t* d_frames, size_t capacity_bytes, uint64_t* d_frame_offsets, uint32_t* d_frame_size,

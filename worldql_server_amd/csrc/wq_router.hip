@@ -133,6 +133,7 @@ int wq_router_destroy(wq_router* h) {
     dispatch_release(h);
     recdispatch_release(h);
     slab_release(h);
+    slab_compact_release(h);
     reply_release(h);
     records_release(h);
     export_release(h);
@@ -881,6 +882,32 @@ int wq_slab_store_device(wq_router* h, const wq_rec_op* d_ops, const wq_rec_op_r
         return set_error(h, WQ_E_INVALID, "slab_store: n_ops must be < 2^31 and n_frames < 2^32 - 1");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_slab_store(h, d_ops, d_op_ref, n_ops, d_frames, d_frame_offsets, n_frames, view, d_cursor, d_counters);
+}
+
+// Do the byte ranges [a, a + na) and [b, b + nb) share a byte? Empty ranges share none.
+static bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+
+int wq_slab_compact_device(wq_router* h, const wq_slab_view* src, const wq_slab_view* dst, uint64_t* d_dst_cursor,
+                           wq_slab_compact_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!src || !dst || !d_dst_cursor) return set_error(h, WQ_E_INVALID, "slab_compact: src, dst or d_dst_cursor is null");
+    if (h->multi) return set_error(h, WQ_E_INVALID, "slab_compact: a multi-GPU handle has no record path");
+    for (const wq_slab_view* v : {src, dst}) {
+        if ((v->n_entries && !v->entries) || (v->n_payload_bytes && !v->payload))
+            return set_error(h, WQ_E_INVALID, "slab_compact: a null array with a non-zero size");
+        // the source arena is only read, at any alignment (as the reply builder reads it)
+        if (((uintptr_t)v->entries | (v == dst ? (uintptr_t)v->payload : 0)) & 15u)
+            return set_error(h, WQ_E_INVALID, "slab_compact: entries and dst's payload must be 16-byte aligned");
+        if (v->n_entries >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "slab_compact: n_entries must be < 2^32 - 1");
+    }
+    if (ranges_overlap(src->entries, src->n_entries * sizeof(wq_slab_entry), dst->entries, dst->n_entries * sizeof(wq_slab_entry)) ||
+        ranges_overlap(src->payload, src->n_payload_bytes, dst->payload, dst->n_payload_bytes))
+        return set_error(h, WQ_E_INVALID, "slab_compact: src and dst overlap (the call is out of place)");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_slab_compact(h, src, dst, d_dst_cursor, d_counters);
 }
 
 int wq_debug_set_ingest_list(wq_router* h, int64_t entries) {

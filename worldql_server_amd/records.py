@@ -8,6 +8,9 @@ fixed as the header says. `GpuRecordStore` is the ctypes binding of the wq_recor
 with the per-record work on the device (wq_records_dispatch_device through ingest.IngestTick).
 `slab_store_np` is the definition of wq_slab_store_device (csrc/wq_slab.hip), which keeps the created
 records' payloads in device memory, and `DeviceRecordSlab` the torch-side owner of that slab.
+`slab_compact_np` is the definition of wq_slab_compact_device (csrc/wq_slab_compact.hip), the slab's canonical
+form: DeviceRecordSlab compacts, exports and loads through it, and DeviceRecordProcessor.snapshot / restore
+with save_snapshot / load_snapshot carry the device record path across a restart.
 """
 from __future__ import annotations
 
@@ -658,8 +661,10 @@ class DeviceRecordProcessor:
     next tick resolves them on the device. A slab entry holds the record's uuid, position, data and flex;
     its world_name is the sanitized name."""
 
-    def __init__(self, store, tick, world_names, dedupe: bool = True):
+    def __init__(self, store, tick, world_names, dedupe: bool = True, compact_at: float | None = None):
         self.store, self.tick, self.router, self.dedupe = store, tick, store.router, dedupe
+        self.compact_at = compact_at   # process_frames's slab: DeviceRecordSlab's policy (None: never compacts)
+        self.totals_base: dict = {}    # what a restored snapshot had counted
         self.names = [n if isinstance(n, str) else bytes(n).decode("utf-8") for n in world_names]
         self.fallback = RecordProcessor(store, WorldIds(), dedupe)
         for n in self.names:
@@ -674,6 +679,8 @@ class DeviceRecordProcessor:
         asked once counts them (the sizing call and the answering call both reject it)."""
         t = self.store.totals()
         t["rejected_queries"] -= self.sizing_rejected
+        for k, v in self.totals_base.items():
+            t[k] += v
         return t
 
     def process(self, data, offsets, now_us: int, d_frames=None, d_offsets=None) -> list:
@@ -806,7 +813,7 @@ class DeviceRecordProcessor:
             d_frames = torch.from_numpy(data.copy() if len(data) else np.zeros(1, np.uint8)).to(dev)[:len(data)]
             d_offsets = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
         if not hasattr(self, "dslab"):
-            self.dslab, self.d_free, self.d_next = DeviceRecordSlab(self.router, dev), [], 0
+            self.dslab, self.d_free, self.d_next = DeviceRecordSlab(self.router, dev, compact_at=self.compact_at), [], 0
         tick.decode(d_frames, d_offsets).dispatch()
         tick.records_dispatch(d_frames, d_offsets, now_us, free_handles=self.d_free[::-1], handle_next=self.d_next)
         cnt, runs = tick.read_records_ctrl()
@@ -902,6 +909,57 @@ class DeviceRecordProcessor:
             self.store.apply(np.array(ops, dtype=REC_OP_DTYPE))
             self._free_dead_device()
 
+    # ---- process_frames's state across a restart ----
+
+    def snapshot(self) -> dict:
+        """What process_frames has built up, as a dict of numpy arrays (save_snapshot writes it): the store's
+        live rows and ops_seen, its region sizes, table size and the dedupe flag, the slab in canonical form
+        (DeviceRecordSlab.export), the free handles in order (the order decides which handle the next create
+        gets) and the next unused handle, the totals so far and the world names as bytes plus offsets. The
+        store's dead list is drained into the slab first."""
+        import torch
+        if not hasattr(self, "dslab"):
+            self.dslab, self.d_free, self.d_next = DeviceRecordSlab(self.router, self.tick.device, compact_at=self.compact_at), [], 0
+        torch.cuda.synchronize()
+        self._free_dead_device()
+        rows, ops_seen = self.store.export_rows()
+        entries, payload = self.dslab.export()
+        names = [n.encode("utf-8") for n in self.names]
+        t = self.totals()
+        return dict(rows=rows, ops_seen=np.array([ops_seen], np.uint64),
+                    store_shape=np.array([*self.store.sizes, self.store.table_size], np.uint32),
+                    dedupe=np.array([1 if self.dedupe else 0], np.uint8), slab_entries=entries, slab_payload=payload,
+                    free=np.array(self.d_free, np.uint32), next=np.array([self.d_next], np.uint64),
+                    totals=np.array([t[f] for f, _ in RecTotals._fields_], np.uint64),
+                    world_bytes=np.frombuffer(b"".join(names), np.uint8).copy(),
+                    world_off=np.cumsum([0] + [len(n) for n in names]).astype(np.uint64))
+
+    def restore(self, snap: dict) -> dict:
+        """A snapshot into this processor, which is fresh and stands over a fresh store of the snapshot's shape
+        (ValueError otherwise): the rows through import_rows, the slab through DeviceRecordSlab.load, which
+        validates it, the world names into the router's table, the free list, the next handle and the totals
+        as they were. Returns the slab's load counters."""
+        shape = [int(v) for v in snap["store_shape"]]
+        if shape != [*self.store.sizes, self.store.table_size] or bool(snap["dedupe"][0]) != bool(self.dedupe):
+            raise ValueError("restore: the snapshot is of a store of another shape or dedupe flag")
+        if hasattr(self, "dslab"):
+            raise ValueError("restore: the processor has been used")
+        off, raw = [int(v) for v in snap["world_off"]], np.asarray(snap["world_bytes"], np.uint8).tobytes()
+        self.names = [raw[a:b].decode("utf-8") for a, b in zip(off[:-1], off[1:])]
+        self.fallback = RecordProcessor(self.store, WorldIds(), self.dedupe)
+        for n in self.names:
+            self.fallback.worlds.intern(n)
+        self.slab, self.free = self.fallback.slab, self.fallback.free
+        self.router.set_worlds(self.names)
+        got = self.store.import_rows(np.asarray(snap["rows"]).view(REC_ROW_DTYPE).reshape(-1), int(snap["ops_seen"][0]))
+        if got["rejected"]:
+            raise ValueError(f"restore: the store rejected {got['rejected']} rows")
+        self.dslab = DeviceRecordSlab(self.router, self.tick.device, compact_at=self.compact_at)
+        cnt = self.dslab.load(np.asarray(snap["slab_entries"]).view(abi.SLAB_ENTRY_DTYPE).reshape(-1), snap["slab_payload"])
+        self.d_free, self.d_next = [int(h) for h in snap["free"]], int(snap["next"][0])
+        self.totals_base = {f: int(v) for (f, _), v in zip(RecTotals._fields_, snap["totals"])}
+        return cnt
+
 
 # ---- the record payload slab (wq_slab_store_device, csrc/wq_slab.hip) ----
 
@@ -965,17 +1023,96 @@ def slab_counters(raw) -> dict:
     return {k: int(c[k]) for k in abi.SLAB_COUNTERS_DTYPE.names}
 
 
+# ---- slab compaction (wq_slab_compact_device, csrc/wq_slab_compact.hip) ----
+
+def slab_compact_np(entries, payload, n_dst_entries: int, n_dst_bytes: int, dst=None):
+    """The definition of wq_slab_compact_device: the header's rules in plain Python. entries
+    (abi.SLAB_ENTRY_DTYPE) and payload (u8) are the source slab, n_dst_entries / n_dst_bytes the sizes of the
+    destination; dst = (entries, payload, cursor) is the destination as it stands before the call (zeros and
+    cursor 0 when None). Returns (entries, payload, cursor, counters): the destination with the call applied,
+    or unchanged after an overflow, and the counters as a dict with abi.SLAB_COMPACT_COUNTERS_DTYPE's fields."""
+    src = np.ascontiguousarray(entries, dtype=abi.SLAB_ENTRY_DTYPE)
+    arena = np.ascontiguousarray(payload, dtype=np.uint8)
+    if dst is None:
+        dst = (np.zeros(n_dst_entries, abi.SLAB_ENTRY_DTYPE), np.zeros(n_dst_bytes, np.uint8), 0)
+    d_ent, d_pay, cursor = np.array(dst[0], dtype=abi.SLAB_ENTRY_DTYPE), np.array(dst[1], dtype=np.uint8), int(dst[2])
+    assert len(d_ent) == n_dst_entries and len(d_pay) == n_dst_bytes
+    n, error, at, need, plan = len(arena), 0, 0, 0, []
+    for i in np.flatnonzero(src["bits"] & np.uint32(abi.SLAB_LIVE)):
+        i, e = int(i), src[i]
+        off, dl, fl = int(e["off"]), int(e["data_len"]), int(e["flex_len"])
+        if off + dl + fl > n:        # Python integers: no wrap
+            error |= abi.SLAB_COMPACT_ERROR_RANGE
+            off = dl = fl = 0
+        plan.append((i, at, off, dl, fl))
+        at += dl + fl
+        need = i + 1
+    total = min(at, 2**64 - 1)
+    overflow = (abi.SLAB_OVERFLOW_ARENA if total > n_dst_bytes else 0) | (abi.SLAB_OVERFLOW_ENTRIES if need > n_dst_entries else 0)
+    if not overflow:
+        d_ent[:] = np.zeros(1, abi.SLAB_ENTRY_DTYPE)[0]
+        for i, to, off, dl, fl in plan:
+            d_ent[i] = src[i]
+            d_ent[i]["off"], d_ent[i]["data_len"], d_ent[i]["flex_len"] = to, dl, fl
+            d_pay[to:to + dl + fl] = arena[off:off + dl + fl]
+        cursor = total
+    counters = dict(n_entries=len(src), n_live=len(plan), bytes_live=total, entries_need=need, overflow=overflow, error=error)
+    return d_ent, d_pay, cursor, counters
+
+
+SNAPSHOT_KEYS = ("rows", "ops_seen", "store_shape", "dedupe", "slab_entries", "slab_payload", "free", "next", "totals",
+                 "world_bytes", "world_off")
+
+
+def save_snapshot(path, snap: dict) -> None:
+    """DeviceRecordProcessor.snapshot's dict in one .npz, without pickle: the structured arrays (rows, slab
+    entries) go in as their bytes."""
+    flat = {k: np.ascontiguousarray(snap[k]) for k in SNAPSHOT_KEYS}
+    for k in ("rows", "slab_entries"):
+        flat[k] = flat[k].view(np.uint8).reshape(-1)
+    with open(path, "wb") as f:
+        np.savez(f, **flat)
+
+
+def load_snapshot(path) -> dict:
+    """save_snapshot's file as the dict DeviceRecordProcessor.restore takes (ValueError: a file that is not one)."""
+    with np.load(path, allow_pickle=False) as z:
+        if set(z.files) != set(SNAPSHOT_KEYS):
+            raise ValueError("load_snapshot: not a record snapshot")
+        snap = {k: z[k] for k in SNAPSHOT_KEYS}
+    if len(snap["rows"]) % REC_ROW_DTYPE.itemsize or len(snap["slab_entries"]) % abi.SLAB_ENTRY_DTYPE.itemsize:
+        raise ValueError("load_snapshot: rows or slab entries are not whole")
+    snap["rows"] = snap["rows"].view(REC_ROW_DTYPE)
+    snap["slab_entries"] = snap["slab_entries"].view(abi.SLAB_ENTRY_DTYPE)
+    return snap
+
+
+def slab_compact_counters(raw) -> dict:
+    """abi.SLAB_COMPACT_COUNTERS_DTYPE bytes as slab_compact_np's counters dict."""
+    c = np.frombuffer(bytes(raw), dtype=abi.SLAB_COMPACT_COUNTERS_DTYPE)[0]
+    return {k: int(c[k]) for k in abi.SLAB_COMPACT_COUNTERS_DTYPE.names}
+
+
 class DeviceRecordSlab:
     """The payload slab in device memory: torch tensors for the entries (abi.SLAB_ENTRY_DTYPE, indexed by
     the store's handle) and the byte arena, and the arena's fill as a device word. `store` is
     Router.slab_store_device with grow-and-retry: the one read-back is the call's counters. `free` clears
-    the live bit of dead handles and adds their payload bytes to the dead count; the arena is never
-    compacted, `dead_bytes` says how much of it nothing refers to any more. `put_host` stores one record
-    the host holds (what the host fallback creates from deferred records)."""
+    the live bit of dead handles and adds their payload bytes to the dead count: `dead_bytes` says how much
+    of the arena nothing refers to any more. `put_host` stores one record the host holds (what the host
+    fallback creates from deferred records).
 
-    def __init__(self, router, device, n_entries: int = 1024, n_payload_bytes: int = 1 << 16):
+    `compact` rewrites the slab through Router.slab_compact_device into fresh tensors, live payloads back to
+    back in handle order, and swaps them in; `export` / `load` are the same call into a buffer the host reads
+    and from one it uploaded. compact_at (None: never, the default) is the opt-in policy: `free` compacts when
+    dead_bytes / cursor reaches it, and a `store` that overflows grows by compacting into the larger arena
+    instead of copying the dead bytes along."""
+
+    def __init__(self, router, device, n_entries: int = 1024, n_payload_bytes: int = 1 << 16, compact_at: float | None = None):
         import torch
         self.router, self.device = router, device
+        self.compact_at = compact_at
+        self.compactions = 0
+        self._floor_bytes = max(n_payload_bytes, 16)   # a compaction does not shrink the arena below it
         # zeros, and waited for: the calls run on the handle's stream, not torch's
         self.entries = torch.zeros(max(n_entries, 1), 8, dtype=torch.int64, device=device)
         self.payload = torch.zeros(max(n_payload_bytes, 16), dtype=torch.uint8, device=device)
@@ -1030,7 +1167,11 @@ class DeviceRecordSlab:
             if not cnt["overflow"]:
                 self.cursor = cnt["cursor"]
                 return cnt
-            self._grow(cnt["entries_need"], cnt["bytes_need"])
+            if self.compact_at is None:
+                self._grow(cnt["entries_need"], cnt["bytes_need"])
+            else:
+                self.compact(min_entries=cnt["entries_need"], extra_bytes=cnt["bytes_stored"])
+                self.grows += 1
         raise RuntimeError(f"slab store: overflow {cnt['overflow']:#x} after growing")
 
     def free(self, handles) -> None:
@@ -1047,6 +1188,74 @@ class DeviceRecordSlab:
         self.dead += torch.where(live, (w7 & 0xFFFFFFFF) + ((w7 >> 32) & 0xFFFFFFFF), torch.zeros_like(w7)).sum()
         self.entries[idx, 5] = w5 & 0x7FFFFFFFFFFFFFFF
         torch.cuda.synchronize()
+        if self.compact_at is not None and self.cursor and self.dead_bytes >= self.compact_at * self.cursor:
+            self.compact()
+
+    # ---- the canonical form: compaction, export, load (Router.slab_compact_device) ----
+
+    def _rewrite(self, src: "abi.SlabView", n_entries: int, n_bytes: int, cursor_ptr: int, extra_bytes: int = 0):
+        """`src` compacted into fresh tensors of at least n_entries / n_bytes, the total into the device word at
+        cursor_ptr; after an overflow the sizes come from the counters and the call is repeated once.
+        Returns (entries, payload, counters): one read-back a call."""
+        import torch
+        for _ in range(2):
+            ent = torch.empty(n_entries, 8, dtype=torch.int64, device=self.device)
+            pay = torch.empty(n_bytes, dtype=torch.uint8, device=self.device)
+            dst = abi.SlabView(entries=ent.data_ptr() if n_entries else None, n_entries=n_entries,
+                               payload=pay.data_ptr() if n_bytes else None, n_payload_bytes=n_bytes)
+            torch.cuda.synchronize()   # the call runs on the handle's stream, not torch's
+            self.router.slab_compact_device(src, dst, cursor_ptr, self.ctrl.data_ptr() + 8)
+            torch.cuda.synchronize()
+            cnt = slab_compact_counters(self.ctrl[8:8 + abi.SLAB_COMPACT_COUNTERS_DTYPE.itemsize].cpu().numpy())
+            if not cnt["overflow"]:
+                return ent, pay, cnt
+            n_entries, n_bytes = max(n_entries, cnt["entries_need"]), max(n_bytes, cnt["bytes_live"] + extra_bytes)
+        raise RuntimeError(f"slab compact: overflow {cnt['overflow']:#x} after resizing")
+
+    def _adopt(self, ent, pay, cnt) -> None:
+        import torch
+        self.entries, self.payload, self.cursor = ent, pay, cnt["bytes_live"]
+        self.dead.zero_()
+        torch.cuda.synchronize()
+
+    def compact(self, min_entries: int = 0, extra_bytes: int = 0) -> dict:
+        """The slab compacted into fresh tensors and swapped in: live payloads back to back in handle order
+        from byte 0, dead entries zeroed, the cursor (device word and mirror) at the live bytes and `dead_bytes`
+        0. The new arena is sized from the host's cursor and one read of `dead`, twice the live bytes plus
+        extra_bytes and not below the constructor's size; the entries keep their count, or grow to
+        min_entries. Returns the call's counters plus "reclaimed", the bytes the cursor fell by."""
+        before = self.cursor
+        live = max(self.cursor - self.dead_bytes, 0)
+        n_entries = self.n_entries if min_entries <= self.n_entries else max(min_entries, 2 * self.n_entries)
+        ent, pay, cnt = self._rewrite(self.view(), n_entries, max(2 * (live + extra_bytes), self._floor_bytes),
+                                      self.ctrl.data_ptr(), extra_bytes)
+        self._adopt(ent, pay, cnt)
+        self.compactions += 1
+        return dict(cnt, reclaimed=before - self.cursor)
+
+    def export(self):
+        """(entries as abi.SLAB_ENTRY_DTYPE, payload u8) in canonical form, as numpy: the entries up to the
+        highest live handle, the live payloads back to back. A sizing call, then the compaction into scratch
+        tensors of exactly that size, read back; the slab itself is not changed."""
+        import torch
+        word = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ent, pay, _ = self._rewrite(self.view(), 0, 0, word.data_ptr())
+        return (ent.cpu().numpy().reshape(-1).view(abi.SLAB_ENTRY_DTYPE).copy(), pay.cpu().numpy().copy())
+
+    def load(self, entries, payload) -> dict:
+        """A slab from the host (what `export` returned, or any entries and arena bytes) uploaded to staging
+        and compacted into this slab's own tensors, which replaces what it held. The call is the validator: an
+        entry whose range leaves `payload` comes out live and empty, with error bit 0 in the returned counters."""
+        import torch
+        e = np.ascontiguousarray(entries, dtype=abi.SLAB_ENTRY_DTYPE)
+        b = np.ascontiguousarray(payload, dtype=np.uint8)
+        s_ent = torch.from_numpy(e.view(np.int64).reshape(-1, 8).copy()).to(self.device)
+        s_pay = torch.from_numpy(b.copy()).to(self.device)
+        src = abi.SlabView(entries=s_ent.data_ptr() if len(e) else None, n_entries=len(e),
+                           payload=s_pay.data_ptr() if len(b) else None, n_payload_bytes=len(b))
+        ent, pay, cnt = self._rewrite(src, max(self.n_entries, len(e)), max(2 * len(b), self._floor_bytes), self.ctrl.data_ptr())
+        self._adopt(ent, pay, cnt)
+        return cnt
 
     def put_host(self, handle: int, record: dict, world: int) -> None:
         """One record from the host under `handle`: {"uuid": (hi, lo), "position", "data" (str or None),

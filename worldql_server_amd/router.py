@@ -95,6 +95,7 @@ def load_library(build_if_missing: bool = True):
         "wq_records_dispatch_device": ([vp, ctypes.POINTER(abi.RecDispatchIn), ctypes.POINTER(abi.RecDispatchOut), vp], i32),
         "wq_frames_build_records_device": ([vp, ctypes.POINTER(abi.FramesSrc), ctypes.POINTER(abi.FramesRecSrc), sz, vp, sz, vp, vp, vp], i32),
         "wq_slab_store_device": ([vp, vp, vp, sz, vp, vp, sz, ctypes.POINTER(abi.SlabView), vp, vp], i32),
+        "wq_slab_compact_device": ([vp, ctypes.POINTER(abi.SlabView), ctypes.POINTER(abi.SlabView), vp, vp], i32),
         "wq_records_open": ([vp, u16, u16, u16, u32], i32),
         "wq_records_close": ([vp], i32),
         "wq_records_apply": ([vp, vp, sz, vp], i32),
@@ -556,6 +557,18 @@ class Router:
                                                   frame_offsets_ptr or None, n_frames,
                                                   ctypes.byref(view) if view is not None else None, cursor_ptr or None,
                                                   counters_ptr or None))
+
+    def slab_compact_device(self, src: "abi.SlabView", dst: "abi.SlabView", dst_cursor_ptr: int,
+                            counters_ptr: int | None = None) -> None:
+        """wq_slab_compact_device: the slab `src` rewritten into `dst` (both abi.SlabView, device memory that
+        does not overlap) in its canonical form: live payloads back to back in handle order, every other
+        entry zero, the total in the device word at dst_cursor_ptr. All or nothing: a dst that is too small
+        is left as it was and the counters (abi.SLAB_COMPACT_COUNTERS_DTYPE, where counters_ptr points) say
+        what suffices. Asynchronous on the handle's stream; nothing is read back. Host definition:
+        records.slab_compact_np."""
+        self._check(self.lib.wq_slab_compact_device(self.h, ctypes.byref(src) if src is not None else None,
+                                                    ctypes.byref(dst) if dst is not None else None, dst_cursor_ptr or None,
+                                                    counters_ptr or None))
 
     def set_ingest_list(self, entries: int) -> None:
         """wq_debug_set_ingest_list: a test hook, the long-string work list's capacity (0: none; negative:
