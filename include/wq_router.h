@@ -1330,6 +1330,101 @@ typedef struct wq_dispatch_counters {
 int wq_ingest_dispatch_device(wq_router* h, const wq_dispatch_in* in, size_t n_frames,
                               const wq_dispatch_out* out, wq_dispatch_counters* d_counters /* nullable */);
 
+/* ---- ingest joins: new senders get their peer ids on the device ----
+ * An AreaSubscribe from a uuid the sender table lacks is WQ_CLS_DEFERRED above: the host reads the uuids
+ * back, assigns ids, rebuilds the whole table with wq_ingest_set_peers and dispatches the suffix again.
+ * Here one call between the decode and the dispatch assigns the ids with the caller's allocator state
+ * (the convention of wq_records_dispatch_device's handles), patches the decode's sender / flags in place
+ * and merges the new uuids into the handle's table, so the dispatch that follows sees no deferred sender
+ * and the next tick's decode resolves the joiners. World-name joins stay deferred and stay the host's.
+ * An extension like the decoder; the host definitions are ingest.join_peers_np / ingest.drop_peers_np and
+ * the arithmetic is csrc/join_ops.hpp.
+ *
+ * wq_ingest_peers_reserve (host call, not per tick; waits for the stream)
+ *   - The sender table gets room for `capacity` entries (existing entries are kept; a capacity below the
+ *     reserved one or below the live count keeps the larger room) and its live count becomes a device
+ *     word the handle owns, which the decode reads. capacity >= 2^32 - 1 is WQ_E_INVALID.
+ *   - wq_ingest_set_peers keeps working as before and keeps the reserved room (n > capacity grows it).
+ *     Without a reserve the handle behaves exactly as before.
+ * wq_ingest_join_device
+ *   - Candidate: a frame with flag bit 0, instruction 4, flag bit 1 (position), not flag bit 4, world
+ *     resolved (bit 5 and world < WQ_WORLD_GLOBAL) and sender not known (bit 6 clear or sender ==
+ *     0xFFFFFFFF): exactly a frame the dispatch classes WQ_CLS_DEFERRED for its sender alone. A subscribe
+ *     whose world did not resolve is no candidate: it stays deferred, and so does its sender. A candidate
+ *     whose uuid the handle's table already holds (the arrays were not decoded against this table) is no
+ *     candidate either and sets error bit 0: the table never holds a uuid twice.
+ *   - Joins: the distinct uuids of the candidates, ordered by the frame index of their first candidate
+ *     (first_frame). Join k gets free_ids[k] for k < n_free, else id_next + (k - n_free); the caller
+ *     passes its free list in pop order. out->j_uuid[16 k], j_id[k], j_frame[k] = first_frame list them.
+ *   - Patch: every frame i with flag bit 0 set and sender not known whose uuid joined gets sender[i] = id
+ *     and flag bit 6, but only when i >= first_frame of that uuid: as in the reference's sequential loop,
+ *     an unsubscribe or heartbeat that precedes a peer's first subscribe sees a peer without an id.
+ *   - Table: the joins are merged into the handle's sender table, keys ascending as before, and the live
+ *     count is updated on the device.
+ *   - All or nothing: with an overflow bit set sender, flags, the table and j_* are untouched and the
+ *     counters say what was needed (n_joined is what would have joined, n_patched 0, n_free_used 0,
+ *     id_next and n_table unchanged). overflow bit 0: more joins than n_free + (id_limit - id_next);
+ *     bit 1: live + joins above the reserved capacity; bit 2: more joins than joined_capacity (looked at
+ *     only when one of j_uuid / j_id / j_frame is given). The frames then stay deferred and the host path
+ *     above still works.
+ *   - wq_join_counters: n_frames, n_candidates, n_joined, n_patched, n_free_used, id_next (after),
+ *     n_table (after), first_join (the first join's frame index; n_frames when none or on overflow),
+ *     overflow, error. error bit 0: a decoded frame's flag and value disagree, as in the dispatch (what
+ *     disagrees counts as unresolved). error bit 1: the handle has no reserved table; the call is then a
+ *     no-op: nothing is written but the counters, with n_frames, error bit 1, first_join = n_frames,
+ *     id_next as given and everything else 0.
+ *   - Asynchronous on the handle's stream, nothing read back, deterministic byte for byte (the only
+ *     atomics are integer adds and ORs into the counters). Scratch lives in the handle, grow-only: 69
+ *     bytes per frame and 12 per 64 frames, 20 bytes per reserved table entry (the table's second buffer
+ *     during a merge) and the sort's temporary storage; a steady-state
+ *     call does no hipMalloc. The passes over the frames have n_frames lanes; the table passes read the
+ *     number of joins on the device and return at once when it is zero. No lane owns a uuid's frames.
+ *   - WQ_E_INVALID, nothing launched: a null handle, in or out; a null instruction, flags, world,
+ *     sender_uuid or sender with n_frames > 0; n_free > 0 without free_ids; n_frames >= 2^32 - 1;
+ *     id_next > id_limit.
+ *   - A multi-GPU handle runs the call on its own stream with the arrays on devices[0], as the decoder.
+ * wq_ingest_drop_peers_device (the leave side)
+ *   - Every table entry whose id is in d_ids[n] is removed by a stable compaction (keys stay ascending)
+ *     and the live count is updated on the device. Ids the table lacks and duplicates are ignored.
+ *     Asynchronous, nothing read back. A server calls it with the ids it gives to wq_remove_peers, before
+ *     those ids go back on its free list: a reused id then never resolves from its old uuid.
+ *   - Counters: n_frames = n, n_patched = the entries removed, n_table (after), first_join = n, error
+ *     bit 1 and a no-op without a reserved table; every other field 0. Scratch: 4 n bytes, 20 bytes per
+ *     reserved entry. WQ_E_INVALID for a null handle, a null d_ids with n > 0 and n >= 2^32 - 1.
+ * wq_ingest_peers_read (host call; waits for the stream)
+ *   - The live table, keys ascending: uuids[16 i], ids[i]. *n is the live count; with both arrays null it
+ *     is only counted (the sizing convention of wq_records_drain_dead); else capacity < *n is WQ_E_INVALID
+ *     with *n set. Works with and without a reserve. For snapshots and tests. */
+typedef struct wq_join_in {          /* device pointers: the arrays wq_frames_decode_device wrote */
+    const uint8_t*  instruction;     /* [n] required */
+    const uint32_t* world;           /* [n] required */
+    const uint8_t*  sender_uuid;     /* [16 n] required */
+    uint8_t*        flags;           /* [n] required, patched in place */
+    uint32_t*       sender;          /* [n] required, patched in place */
+    const uint32_t* free_ids;        /* [n_free] nullable with n_free 0: the free list in pop order */
+    uint32_t        n_free, id_next, id_limit, pad_;
+} wq_join_in;                /* 64 bytes */
+
+typedef struct wq_join_out {         /* device pointers, each nullable */
+    uint8_t*  j_uuid;                /* [16 joined_capacity] */
+    uint32_t* j_id;                  /* [joined_capacity] */
+    uint32_t* j_frame;               /* [joined_capacity] */
+    uint32_t  joined_capacity, pad_;
+} wq_join_out;               /* 32 bytes */
+
+typedef struct wq_join_counters {
+    uint64_t n_frames, n_candidates, n_joined, n_patched, n_free_used;
+    uint64_t id_next, n_table, first_join, overflow, error;
+} wq_join_counters;          /* 80 bytes */
+
+int wq_ingest_peers_reserve(wq_router* h, size_t capacity);
+int wq_ingest_join_device(wq_router* h, const wq_join_in* in, size_t n_frames, const wq_join_out* out,
+                          wq_join_counters* d_counters /* nullable */);
+int wq_ingest_drop_peers_device(wq_router* h, const uint32_t* d_ids, size_t n,
+                                wq_join_counters* d_counters /* nullable */);
+int wq_ingest_peers_read(wq_router* h, uint8_t* uuids /* host, [16 capacity] */, uint32_t* ids /* host */,
+                         size_t capacity, size_t* n);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

@@ -160,6 +160,26 @@ class DispatchOut(ctypes.Structure):  # struct wq_dispatch_out: device pointers,
 assert ctypes.sizeof(DispatchIn) == 64 and ctypes.sizeof(DispatchOut) == 120
 assert DISPATCH_RUN_DTYPE.itemsize == 20 and DISPATCH_COUNTERS_DTYPE.itemsize == 168
 
+# ---- ingest joins (wq_ingest_join_device, wq_ingest_drop_peers_device) ----
+JOIN_ERROR_DISAGREE, JOIN_ERROR_NO_TABLE = 1, 2                 # wq_join_counters.error bits 0 and 1
+JOIN_OVERFLOW_IDS, JOIN_OVERFLOW_TABLE, JOIN_OVERFLOW_OUT = 1, 2, 4   # wq_join_counters.overflow bits 0 - 2
+# struct wq_join_counters: 80 bytes
+JOIN_COUNTERS_DTYPE = np.dtype([(k, np.uint64) for k in ("n_frames", "n_candidates", "n_joined", "n_patched", "n_free_used",
+                                                         "id_next", "n_table", "first_join", "overflow", "error")])
+
+
+class JoinIn(ctypes.Structure):  # struct wq_join_in: device pointers; flags and sender are patched in place
+    _fields_ = [(k, ctypes.c_void_p) for k in ("instruction", "world", "sender_uuid", "flags", "sender", "free_ids")] + \
+               [(k, ctypes.c_uint32) for k in ("n_free", "id_next", "id_limit", "pad_")]
+
+
+class JoinOut(ctypes.Structure):  # struct wq_join_out: device pointers, each nullable
+    _fields_ = [(k, ctypes.c_void_p) for k in ("j_uuid", "j_id", "j_frame")] + \
+               [("joined_capacity", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(JoinIn) == 64 and ctypes.sizeof(JoinOut) == 32 and JOIN_COUNTERS_DTYPE.itemsize == 80
+
 
 # ---- record dispatch (wq_records_dispatch_device) ----
 # WQ_RCLS_*: the class of a listed frame, in the order of wq_recdisp_counters' per-class counts

@@ -37,9 +37,11 @@ __global__ __launch_bounds__(kDecBlock) void k_decode_walk(const uint8_t* __rest
                                                            const uint64_t* __restrict__ fo, uint64_t n,
                                                            uint64_t n_frame_bytes, DecList list, DecTables t,
                                                            wq_ingest_out out, uint32_t* __restrict__ word,
-                                                           wq_ingest_counters* ctrl) {
+                                                           wq_ingest_counters* ctrl,
+                                                           const uint32_t* __restrict__ live_peers) {
     const uint64_t i = (uint64_t)blockIdx.x * kDecBlock + threadIdx.x;
     if (i >= n) return;
+    if (live_peers) t.n_peers = *live_peers;  // a reserved sender table: its live count is the device's
     uint32_t err = 0;
     word[i] = dec_walk(frames, fo, i, n, n_frame_bytes, list, t, out, &err);
     if (err) atomicOr(&ctrl->error, err);
@@ -107,8 +109,13 @@ int ingest_set_world_index(wq_router* h, const uint8_t* names, const uint32_t* o
 // The sender table (the handle's device is current; arguments validated). Like the world table: waited
 // for, ordered behind earlier decodes and before later ones, and an error leaves no table, not a torn one.
 int ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, uint32_t n) {
+    const bool reserved = h->ing_live.p != nullptr;  // wq_ingest_peers_reserve: the live count is a device word
     if (n == 0) {
         h->ing_n_peers = 0;
+        if (reserved) {
+            WQ_HIP(h, hipStreamSynchronize(h->stream));
+            WQ_HIP(h, hipMemcpy(h->ing_live.p, &n, 4, hipMemcpyHostToDevice));
+        }
         return WQ_OK;
     }
     std::vector<uint64_t> hi, lo;
@@ -116,15 +123,22 @@ int ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, ui
     if (!dec_peer_index(uuids, ids, n, &hi, &lo, &id))
         return set_error(h, WQ_E_INVALID, "ingest_set_peers: a uuid occurs twice");
     WQ_HIP(h, hipStreamSynchronize(h->stream));  // a growing buffer is freed: nothing may still read it
-    WQ_ALLOC(h, h->ing_phi, (size_t)n * 8);
-    WQ_ALLOC(h, h->ing_plo, (size_t)n * 8);
-    WQ_ALLOC(h, h->ing_pid, (size_t)n * 4);
+    const size_t room = reserved && h->ing_cap > n ? h->ing_cap : n;  // the reserved room is kept, or grown
+    WQ_ALLOC(h, h->ing_phi, room * 8);
+    WQ_ALLOC(h, h->ing_plo, room * 8);
+    WQ_ALLOC(h, h->ing_pid, room * 4);
     h->ing_n_peers = 0;
+    if (reserved) {
+        const uint32_t none = 0;
+        WQ_HIP(h, hipMemcpy(h->ing_live.p, &none, 4, hipMemcpyHostToDevice));
+        h->ing_cap = (uint32_t)room;
+    }
     WQ_HIP(h, hipMemcpyAsync(h->ing_phi.p, hi.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
     WQ_HIP(h, hipMemcpyAsync(h->ing_plo.p, lo.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
     WQ_HIP(h, hipMemcpyAsync(h->ing_pid.p, id.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     WQ_HIP(h, hipStreamSynchronize(h->stream));
     h->ing_n_peers = n;
+    if (reserved) WQ_HIP(h, hipMemcpy(h->ing_live.p, &n, 4, hipMemcpyHostToDevice));
     return WQ_OK;
 }
 
@@ -158,7 +172,8 @@ int launch_frames_decode(wq_router* h, const uint8_t* d_frames, const uint64_t* 
         uint32_t* word = h->ing_word.as<uint32_t>();
         const unsigned blocks = (unsigned)((n_frames + kDecBlock - 1) / kDecBlock);
         hipLaunchKernelGGL(k_decode_walk, dim3(blocks), dim3(kDecBlock), 0, s, d_frames, d_frame_offsets,
-                           (uint64_t)n_frames, (uint64_t)n_frame_bytes, list, t, *out, word, ctrl);
+                           (uint64_t)n_frames, (uint64_t)n_frame_bytes, list, t, *out, word, ctrl,
+                           h->ing_live.as<const uint32_t>());
         WQ_HIP(h, hipGetLastError());
         if (cap) {
             const unsigned bx = cap < kDecListBlocks ? cap : kDecListBlocks;

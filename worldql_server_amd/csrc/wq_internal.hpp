@@ -299,6 +299,12 @@ struct wq_router {
     wq::DevBuf ing_word, ing_list, ing_ctrl, ing_whash, ing_wid, ing_phi, ing_plo, ing_pid;
     uint32_t ing_n_peers = 0;
     int64_t ing_list_cap = -1;  // wq_debug_set_ingest_list (negative: the default)
+    // ingest joins (wq_join.hip). wq_ingest_peers_reserve: ing_cap > 0 is the sender table's room in
+    // entries and ing_live holds its live count, one device u32 the decode reads in place of ing_n_peers.
+    // A call's scratch (per frame and per table entry), the table's copy during a merge or a compaction,
+    // and the control block between the passes.
+    wq::DevBuf ing_live, join_ws, join_tab, join_ctrl;
+    uint32_t ing_cap = 0;
     // ingest dispatch (wq_dispatch.hip): per frame its class between the passes; one DspSum per 1,024
     // frames and the total behind them
     wq::DevBuf dsp_cls, dsp_sum;
@@ -452,6 +458,14 @@ int ingest_set_peers(wq_router* h, const uint8_t* uuids, const uint32_t* ids, ui
 int launch_frames_decode(wq_router* h, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n_frames,
                          size_t n_frame_bytes, const wq_ingest_out* out, wq_ingest_counters* d_counters);
 void ingest_release(wq_router* h);
+// wq_join.hip: the sender table's reserve and read (both wait for the stream), the join and the drop on
+// device arrays (asynchronous; arguments validated), and the release of their scratch.
+int ingest_peers_reserve(wq_router* h, size_t capacity);
+int ingest_peers_read(wq_router* h, uint8_t* uuids, uint32_t* ids, size_t capacity, size_t* n);
+int launch_ingest_join(wq_router* h, const wq_join_in* in, size_t n_frames, const wq_join_out* out,
+                       wq_join_counters* d_counters);
+int launch_ingest_drop(wq_router* h, const uint32_t* d_ids, size_t n, wq_join_counters* d_counters);
+void join_release(wq_router* h);
 // wq_dispatch.hip: the dispatch on device arrays (asynchronous) and the release of its scratch.
 int launch_ingest_dispatch(wq_router* h, const wq_dispatch_in* in, size_t n_frames, const wq_dispatch_out* out,
                            wq_dispatch_counters* d_counters);

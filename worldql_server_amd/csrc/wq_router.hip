@@ -130,6 +130,7 @@ int wq_router_destroy(wq_router* h) {
     pack_release(h);
     frames_release(h);
     ingest_release(h);
+    join_release(h);
     dispatch_release(h);
     recdispatch_release(h);
     slab_release(h);
@@ -823,6 +824,41 @@ int wq_ingest_dispatch_device(wq_router* h, const wq_dispatch_in* in, size_t n_f
     if (n_frames >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_dispatch: n_frames must be < 2^32 - 1");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_ingest_dispatch(h, in, n_frames, out, d_counters);
+}
+
+int wq_ingest_peers_reserve(wq_router* h, size_t capacity) {
+    if (!h) return WQ_E_INVALID;
+    if (capacity >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_peers_reserve: capacity must be < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return ingest_peers_reserve(h, capacity);
+}
+
+int wq_ingest_peers_read(wq_router* h, uint8_t* uuids, uint32_t* ids, size_t capacity, size_t* n) {
+    if (!h) return WQ_E_INVALID;
+    if (!n) return set_error(h, WQ_E_INVALID, "ingest_peers_read: n is null");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return ingest_peers_read(h, uuids, ids, capacity, n);
+}
+
+int wq_ingest_join_device(wq_router* h, const wq_join_in* in, size_t n_frames, const wq_join_out* out,
+                          wq_join_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!in || !out) return set_error(h, WQ_E_INVALID, "ingest_join: in or out is null");
+    if (n_frames && (!in->instruction || !in->flags || !in->world || !in->sender || !in->sender_uuid))
+        return set_error(h, WQ_E_INVALID, "ingest_join: a null array with a non-zero size");
+    if (in->n_free && !in->free_ids) return set_error(h, WQ_E_INVALID, "ingest_join: n_free without free_ids");
+    if (n_frames >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_join: n_frames must be < 2^32 - 1");
+    if (in->id_next > in->id_limit) return set_error(h, WQ_E_INVALID, "ingest_join: id_next is above id_limit");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_ingest_join(h, in, n_frames, out, d_counters);
+}
+
+int wq_ingest_drop_peers_device(wq_router* h, const uint32_t* d_ids, size_t n, wq_join_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (n && !d_ids) return set_error(h, WQ_E_INVALID, "ingest_drop_peers: d_ids is null");
+    if (n >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_drop_peers: n must be < 2^32 - 1");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_ingest_drop(h, d_ids, n, d_counters);
 }
 
 int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,

@@ -15,6 +15,12 @@ the dict `decode_frames_np` returns. `IngestTick.dispatch` enqueues the device c
 arrays and `IngestTick.process` reads the counters and the run table, the tick's one read-back, and
 issues the runs in order.
 
+`join_peers_np` and `drop_peers_np` are the definitions of wq_ingest_join_device and
+wq_ingest_drop_peers_device (csrc/wq_join.hip): between decode and dispatch the subscribes of senders the
+table lacks get their peer ids by the caller's allocator state, sender and flags are patched in place and
+the handle's sender table takes the joins; the drop is the leave side. `IngestTick.join` enqueues the call
+on the decode's arrays with its counters beside the dispatch's, so `process` still has one read-back.
+
 `records_dispatch_np` is the definition of what wq_records_dispatch_device writes (csrc/wq_recdispatch.hip):
 the record frames of the dispatch's database list walked record by record into the ops and query rows of
 the record store, the deferred list and the run table that reproduces records.RecordProcessor.process's
@@ -267,6 +273,103 @@ def dispatch_counters(raw) -> dict:
     """abi.DISPATCH_COUNTERS_DTYPE bytes as dispatch_np's counters dict."""
     c = np.asarray(raw).view(np.uint8)[:abi.DISPATCH_COUNTERS_DTYPE.itemsize].view(abi.DISPATCH_COUNTERS_DTYPE)[0]
     return {k: [int(v) for v in c[k]] if k == "side_begin" else int(c[k]) for k in abi.DISPATCH_COUNTERS_DTYPE.names}
+
+
+# ---- ingest joins: new senders get their ids between decode and dispatch (wq_ingest_join_device) ----
+def _table_dict(table_uuids, table_ids):
+    rows = uuid_rows(table_uuids if table_uuids is not None else [])
+    ids = np.arange(len(rows), dtype=np.uint32) if table_ids is None else np.asarray(table_ids, dtype=np.uint32)
+    return {r.tobytes(): int(i) for r, i in zip(rows, ids)}
+
+
+def _table_arrays(table: dict):
+    keys = sorted(table)   # bytes compare as the big-endian 128-bit keys do
+    u = np.frombuffer(b"".join(keys), dtype=np.uint8).reshape(-1, 16).copy() if keys else np.zeros((0, 16), np.uint8)
+    return u, np.array([table[k] for k in keys], dtype=np.uint32)
+
+
+def join_peers_np(decoded, table_uuids, table_ids, free_ids, id_next, id_limit, capacity, joined_capacity=None):
+    """The definition of wq_ingest_join_device: a plain loop over the frames of the dict decode_frames_np
+    returns (instruction, flags, world, sender, sender_uuid). A frame classify_frame calls CLS_DEFERRED
+    whose world resolved is a candidate; the first candidate of a uuid is its join and takes the next id
+    (free_ids in order, then id_next upwards; a "candidate" whose uuid the table already holds is none and
+    sets error bit 0); from that frame on, every decoded frame of the uuid whose
+    sender is not known gets the id and the SENDER_KNOWN bit. table_uuids / table_ids: the sender table
+    (ids None: the index); capacity: its reserved room (None: no reserved table, the call is a no-op with
+    error bit 1); joined_capacity None: the j_* arrays are not given. Returns a dict of sender, flags
+    (patched copies), j_uuid u8[k, 16], j_id, j_frame u32[k], table (uuids ascending, ids) and counters (a
+    dict of abi.JOIN_COUNTERS_DTYPE's fields). With an overflow bit set nothing changes and j_* are empty."""
+    ins_a, flags_a = np.asarray(decoded["instruction"], np.uint8), np.array(decoded["flags"], np.uint8, copy=True)
+    world_a, sender_a = np.asarray(decoded["world"], np.uint32), np.array(decoded["sender"], np.uint32, copy=True)
+    uuid_a = np.ascontiguousarray(decoded["sender_uuid"], np.uint8).reshape(-1, 16)
+    n = len(ins_a)
+    free = [int(v) for v in (free_ids if free_ids is not None else [])]
+    table = _table_dict(table_uuids, table_ids)
+    empty = dict(j_uuid=np.zeros((0, 16), np.uint8), j_id=np.zeros(0, np.uint32), j_frame=np.zeros(0, np.uint32))
+    cnt = {k: 0 for k in abi.JOIN_COUNTERS_DTYPE.names}
+    cnt.update(n_frames=n, id_next=int(id_next), first_join=n)
+    if capacity is None:
+        cnt["error"] = abi.JOIN_ERROR_NO_TABLE
+        return dict(sender=sender_a, flags=flags_a, table=_table_arrays(table), counters=cnt, **empty)
+    joined: dict = {}            # uuid bytes -> id, in join order
+    j_frame, patched, error, n_cand = [], [], 0, 0
+    for i in range(n):
+        f, w, s = int(flags_a[i]), int(world_a[i]), int(sender_a[i])
+        cls, e = classify_frame(int(ins_a[i]), f, w, s)
+        error |= e
+        if cls == abi.CLS_BAD or (f & SENDER_KNOWN and s != NO_PEER):
+            continue
+        u = uuid_a[i].tobytes()
+        if cls == abi.CLS_DEFERRED and f & WORLD_KNOWN and w < abi.WORLD_GLOBAL:
+            if u in table:          # the flags and the table disagree: no candidate, the frame is the host's
+                error |= abi.JOIN_ERROR_DISAGREE
+                continue
+            n_cand += 1
+            if u not in joined:
+                k = len(joined)
+                joined[u] = free[k] if k < len(free) else int(id_next) + (k - len(free))
+                j_frame.append(i)
+        if u in joined:
+            patched.append(i)
+    k = len(joined)
+    overflow = (abi.JOIN_OVERFLOW_IDS if k > len(free) + (int(id_limit) - int(id_next)) else 0) | \
+               (abi.JOIN_OVERFLOW_TABLE if len(table) + k > int(capacity) else 0) | \
+               (abi.JOIN_OVERFLOW_OUT if joined_capacity is not None and k > int(joined_capacity) else 0)
+    cnt.update(n_candidates=n_cand, n_joined=k, overflow=overflow, error=error, n_table=len(table))
+    if overflow:
+        return dict(sender=sender_a, flags=flags_a, table=_table_arrays(table), counters=cnt, **empty)
+    for i in patched:
+        sender_a[i] = joined[uuid_a[i].tobytes()]
+        flags_a[i] |= SENDER_KNOWN
+    table.update(joined)
+    used = min(k, len(free))
+    cnt.update(n_patched=len(patched), n_free_used=used, id_next=int(id_next) + k - used, n_table=len(table),
+               first_join=j_frame[0] if k else n)
+    return dict(sender=sender_a, flags=flags_a, table=_table_arrays(table), counters=cnt,
+                j_uuid=np.frombuffer(b"".join(joined), dtype=np.uint8).reshape(-1, 16).copy() if k else empty["j_uuid"],
+                j_id=np.array(list(joined.values()), dtype=np.uint32), j_frame=np.array(j_frame, dtype=np.uint32))
+
+
+def drop_peers_np(table_uuids, table_ids, ids, reserved=True):
+    """The definition of wq_ingest_drop_peers_device: the table without the entries whose id is listed, and
+    the counters (n_frames: the ids given, n_patched: the entries removed, n_table: what is left)."""
+    table = _table_dict(table_uuids, table_ids)
+    ids = [int(v) for v in ids]
+    cnt = {k: 0 for k in abi.JOIN_COUNTERS_DTYPE.names}
+    cnt.update(n_frames=len(ids), first_join=len(ids))
+    if not reserved:
+        cnt["error"] = abi.JOIN_ERROR_NO_TABLE
+        return dict(table=_table_arrays(table), counters=cnt)
+    gone = set(ids)
+    kept = {u: i for u, i in table.items() if i not in gone}
+    cnt.update(n_patched=len(table) - len(kept), n_table=len(kept))
+    return dict(table=_table_arrays(kept), counters=cnt)
+
+
+def join_counters(raw) -> dict:
+    """abi.JOIN_COUNTERS_DTYPE bytes as join_peers_np's counters dict."""
+    c = np.asarray(raw).view(np.uint8)[:abi.JOIN_COUNTERS_DTYPE.itemsize].view(abi.JOIN_COUNTERS_DTYPE)[0]
+    return {k: int(c[k]) for k in abi.JOIN_COUNTERS_DTYPE.names}
 
 
 # ---- the record dispatch: the record frames of a tick to store ops and queries (wq_records_dispatch_device) ----
@@ -585,6 +688,8 @@ class IngestTick:
         self.router, self.device, self.cap, self.n = router, device, 0, 0
         self.buf: dict = {}
         self.counters = torch.zeros(INGEST_COUNTERS_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        # the control buffer's room in run entries and join rows; the frames of the tick's join(), None without one
+        self.runs_cap, self.join_cap, self._join_n, self.join_counters = -1, 0, None, None
         self._grow(capacity)
 
     def _grow(self, n: int) -> None:
@@ -601,6 +706,7 @@ class IngestTick:
         n = offsets.numel() - 1 if n_frames is None else n_frames
         self._grow(n)
         self.n = n
+        self._join_n = None   # a new tick: the control buffer holds no join of it yet
         self.router.decode_frames_device(frames.data_ptr() if frames.numel() else None, offsets.data_ptr(), n,
                                          frames.numel() if n_frame_bytes is None else n_frame_bytes, self.out,
                                          self.counters.data_ptr())
@@ -644,11 +750,24 @@ class IngestTick:
             # empty, not zeros: a fill would run on torch's stream, beside the call on the handle's
             self.dbuf = {k: torch.empty(max(self.dcap * w, 8), dtype=torch.uint8, device=self.device)
                          for k, w in self._DSPEC.items()}
-        if runs_capacity > getattr(self, "runs_cap", -1):
-            self.runs_cap = max(runs_capacity, 2 * getattr(self, "runs_cap", 0))
-            # the counters and the run table in one buffer: process() reads both with one copy
-            self.dctrl = torch.empty(abi.DISPATCH_COUNTERS_DTYPE.itemsize + 20 * max(self.runs_cap, 1), dtype=torch.uint8,
-                                     device=self.device)
+        self._grow_ctrl(runs_capacity, 0)
+
+    _CHEAD = abi.DISPATCH_COUNTERS_DTYPE.itemsize + abi.JOIN_COUNTERS_DTYPE.itemsize   # both counters, then the runs
+
+    def _grow_ctrl(self, runs_capacity: int, joined_capacity: int) -> None:
+        """The control buffer: the dispatch's counters, the join's counters, the run table, then j_id / j_frame /
+        j_uuid. process() reads both counters and the run table with one copy."""
+        import torch
+        if runs_capacity <= self.runs_cap and joined_capacity <= self.join_cap:
+            return
+        if self._join_n is not None:
+            raise ValueError("the control buffer would grow over a pending join: pass runs_capacity to join()")
+        if runs_capacity > self.runs_cap:
+            self.runs_cap = max(runs_capacity, 2 * self.runs_cap)
+        if joined_capacity > self.join_cap:
+            self.join_cap = max(joined_capacity, 2 * self.join_cap)
+        self._j_at = (self._CHEAD + 20 * max(self.runs_cap, 1) + 7) // 8 * 8
+        self.dctrl = torch.empty(self._j_at + 24 * self.join_cap + 8, dtype=torch.uint8, device=self.device)
 
     def dispatch(self, runs_capacity: int | None = None, last_seen=None, now: int = 0) -> "IngestTick":
         """Enqueues wq_ingest_dispatch_device on the arrays decode() left; nothing is read back. The rows, the
@@ -662,22 +781,64 @@ class IngestTick:
         self.d_in = abi.DispatchIn(instruction=o.instruction, flags=o.flags, world=o.world, sender=o.sender, repl=o.repl,
                                    pos=o.pos, last_seen=None if last_seen is None else last_seen.data_ptr(),
                                    n_last_seen=0 if last_seen is None else last_seen.numel(), now=now)
-        csize = abi.DISPATCH_COUNTERS_DTYPE.itemsize
         self.d_out = abi.DispatchOut(**{k: t.data_ptr() for k, t in self.dbuf.items()},
-                                     runs=self.dctrl.data_ptr() + csize if self.d_runs_capacity else None,
+                                     runs=self.dctrl.data_ptr() + self._CHEAD if self.d_runs_capacity else None,
                                      runs_capacity=self.d_runs_capacity)
         self.router.dispatch_device(self.d_in, n, self.d_out, self.dctrl.data_ptr())
         return self
+
+    # ---- the joins: new senders get their ids between decode() and dispatch() (wq_ingest_join_device) ----
+    def join(self, free_ids, id_next: int, id_limit: int, joined_capacity: int | None = None,
+             runs_capacity: int | None = None) -> "IngestTick":
+        """Enqueues wq_ingest_join_device on the arrays decode() left, before dispatch(): sender and flags are
+        patched in place and the handle's sender table (Router.reserve_peers) takes the joins. free_ids: a
+        uint32 device tensor in pop order, or None. The counters and j_uuid / j_id / j_frame
+        (joined_capacity rows, default n) sit in the dispatch's control buffer, so process() still has one
+        read-back: it leaves the counters in `join_counters`; read_join() fetches the rows. runs_capacity:
+        what dispatch() will be given, when that is more than n + 1."""
+        n = self.n
+        jc = n if joined_capacity is None else joined_capacity
+        self._join_n = None
+        self._grow_ctrl(n + 1 if runs_capacity is None else runs_capacity, jc)
+        o, base = self.out, self.dctrl.data_ptr() + self._j_at
+        self.j_capacity = jc
+        self.j_in = abi.JoinIn(instruction=o.instruction, world=o.world, sender_uuid=o.sender_uuid, flags=o.flags,
+                               sender=o.sender, free_ids=None if free_ids is None or not free_ids.numel() else free_ids.data_ptr(),
+                               n_free=0 if free_ids is None else free_ids.numel(), id_next=id_next, id_limit=id_limit)
+        self.j_out = abi.JoinOut(j_id=base, j_frame=base + 4 * self.join_cap, j_uuid=base + 8 * self.join_cap,
+                                 joined_capacity=jc)
+        self.router.join_peers_device(self.j_in, n, self.j_out, self.dctrl.data_ptr() + abi.DISPATCH_COUNTERS_DTYPE.itemsize)
+        self._join_n = n
+        return self
+
+    def read_join(self) -> dict:
+        """The join's patched sender / flags, its rows and counters as numpy arrays shaped like join_peers_np's
+        (synchronizes; for tests, and for the host's PeerIds.adopt in a tick with joins)."""
+        import torch
+        torch.cuda.synchronize()
+        c0 = abi.DISPATCH_COUNTERS_DTYPE.itemsize
+        cnt = join_counters(self.dctrl[c0:self._CHEAD].cpu().numpy())
+        k = 0 if cnt["overflow"] or cnt["error"] & abi.JOIN_ERROR_NO_TABLE else cnt["n_joined"]
+        a, J = self._j_at, self.join_cap
+        raw = self.dctrl[a:a + 24 * J].cpu().numpy() if k else np.zeros(24 * J, np.uint8)
+        n = self.n
+        return dict(counters=cnt, j_id=raw[:4 * k].view(np.uint32).copy(), j_frame=raw[4 * J:4 * J + 4 * k].view(np.uint32).copy(),
+                    j_uuid=raw[8 * J:8 * J + 16 * k].reshape(k, 16).copy(),
+                    sender=self.buf["sender"][:4 * n].cpu().numpy().view(np.uint32),
+                    flags=self.buf["flags"][:n].cpu().numpy())
 
     def _read_ctrl(self):
         """The counters and the run table: one copy for tables of up to RUNS_FIRST_READ entries. Waits for
         the device first, as read() does: the handle's stream is not torch's."""
         import torch
         torch.cuda.synchronize()
-        csize = abi.DISPATCH_COUNTERS_DTYPE.itemsize
+        csize = self._CHEAD
         first = min(self.d_runs_capacity, self.RUNS_FIRST_READ)
         raw = self.dctrl[:csize + 20 * first].cpu().numpy()
         cnt = dispatch_counters(raw)
+        # the join's counters of this tick, None without a join() since decode()
+        self.join_counters = join_counters(raw[abi.DISPATCH_COUNTERS_DTYPE.itemsize:csize]) \
+            if self._join_n is not None else None
         have = min(cnt["n_runs"] + 1, self.d_runs_capacity)
         if have > first:
             raw = self.dctrl[:csize + 20 * have].cpu().numpy()

@@ -89,6 +89,10 @@ def load_library(build_if_missing: bool = True):
         "wq_frames_decode_device": ([vp, vp, vp, sz, sz, ctypes.POINTER(abi.IngestOut), vp], i32),
         "wq_debug_set_ingest_list": ([vp, ctypes.c_int64], i32),
         "wq_ingest_dispatch_device": ([vp, ctypes.POINTER(abi.DispatchIn), sz, ctypes.POINTER(abi.DispatchOut), vp], i32),
+        "wq_ingest_peers_reserve": ([vp, sz], i32),
+        "wq_ingest_join_device": ([vp, ctypes.POINTER(abi.JoinIn), sz, ctypes.POINTER(abi.JoinOut), vp], i32),
+        "wq_ingest_drop_peers_device": ([vp, vp, sz, vp], i32),
+        "wq_ingest_peers_read": ([vp, vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                          ctypes.POINTER(sz)], i32),
@@ -518,6 +522,40 @@ class Router:
         self._check(self.lib.wq_ingest_dispatch_device(self.h, ctypes.byref(src) if src is not None else None, n_frames,
                                                        ctypes.byref(out) if out is not None else None,
                                                        counters_ptr or None))
+
+    # ---- ingest joins (include/wq_router.h, "ingest joins"; host definition: ingest.join_peers_np) ----
+    def reserve_peers(self, capacity: int) -> None:
+        """wq_ingest_peers_reserve: room for `capacity` entries in the sender table, whose live count becomes
+        a device word (join_peers_device and drop_peers_device change it, the decode reads it). Existing
+        entries are kept; set_ingest_peers keeps working. Waits for the handle's stream."""
+        self._check(self.lib.wq_ingest_peers_reserve(self.h, capacity))
+
+    def join_peers_device(self, src: "abi.JoinIn", n_frames: int, out: "abi.JoinOut",
+                          counters_ptr: int | None = None) -> None:
+        """wq_ingest_join_device: between decode_frames_device and dispatch_device. The subscribes of
+        senders the table lacks (abi.JoinIn: the decode's instruction, world, sender_uuid, and flags /
+        sender, which are patched in place; the allocator state free_ids / n_free / id_next / id_limit) get
+        their ids, the joins are listed in `out` (abi.JoinOut, each nullable) and merged into the handle's
+        sender table. All or nothing on overflow. Asynchronous on the handle's stream; the counters
+        (abi.JOIN_COUNTERS_DTYPE) stay where counters_ptr points. Host definition: ingest.join_peers_np."""
+        self._check(self.lib.wq_ingest_join_device(self.h, ctypes.byref(src) if src is not None else None, n_frames,
+                                                   ctypes.byref(out) if out is not None else None, counters_ptr or None))
+
+    def drop_peers_device(self, ids_ptr: int | None, n: int, counters_ptr: int | None = None) -> None:
+        """wq_ingest_drop_peers_device: every sender-table entry whose id is among the n device u32 at ids_ptr
+        is removed (absent ids and duplicates are ignored). Asynchronous on the handle's stream. Host
+        definition: ingest.drop_peers_np."""
+        self._check(self.lib.wq_ingest_drop_peers_device(self.h, ids_ptr or None, n, counters_ptr or None))
+
+    def read_peers(self):
+        """wq_ingest_peers_read: the live sender table as (uuids u8[n, 16] ascending, ids u32[n]). Waits for
+        the handle's stream."""
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.wq_ingest_peers_read(self.h, None, None, 0, ctypes.byref(n)))
+        u, i = np.zeros((n.value, 16), np.uint8), np.zeros(n.value, np.uint32)
+        if n.value:
+            self._check(self.lib.wq_ingest_peers_read(self.h, u.ctypes.data, i.ctypes.data, n.value, ctypes.byref(n)))
+        return u, i
 
     def records_dispatch_device(self, src: "abi.RecDispatchIn", out: "abi.RecDispatchOut",
                                 counters_ptr: int | None = None) -> None:

@@ -87,6 +87,32 @@ class PeerIds:
             self._free.append(pid)
         return pid
 
+    def free_in_pop_order(self) -> list:
+        """The free ids in the order `id` would hand them out: what wq_ingest_join_device takes as free_ids
+        (id_next is `high_water`)."""
+        return self._free[::-1]
+
+    def adopt(self, peers, ids) -> None:
+        """Records ids the device assigned (wq_ingest_join_device's j_uuid / j_id, in join order). They must
+        be what `id` would have handed out for these peers in this order; anything else raises ValueError
+        and leaves the map as it was."""
+        peers, ids = list(peers), [int(i) for i in ids]
+        if len(peers) != len(ids):
+            raise ValueError("adopt: one id per peer")
+        if len(set(peers)) != len(peers) or any(p in self._ids for p in peers):
+            raise ValueError("adopt: a peer that already has an id, or occurs twice")
+        n_free = min(len(self._free), len(ids))
+        want = self._free[::-1][:n_free] + list(range(len(self._peers), len(self._peers) + len(ids) - n_free))
+        if ids != want:
+            raise ValueError(f"adopt: ids {ids[:8]}... are not what id() hands out ({want[:8]}...)")
+        for p, pid in zip(peers, ids):
+            if self._free:
+                self._free.pop()
+                self._peers[pid] = p
+            else:
+                self._peers.append(p)
+            self._ids[p] = pid
+
     @property
     def high_water(self) -> int:
         """Ids ever handed out at once: per-peer device arrays need this many entries."""
