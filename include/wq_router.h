@@ -1425,6 +1425,111 @@ int wq_ingest_drop_peers_device(wq_router* h, const uint32_t* d_ids, size_t n,
 int wq_ingest_peers_read(wq_router* h, uint8_t* uuids /* host, [16 capacity] */, uint32_t* ids /* host */,
                          size_t capacity, size_t* n);
 
+/* ---- ingest leaves: stale and disconnected senders leave on the device ----
+ * The dispatch stamps last_seen[sender] = now for every heartbeat, and the join brings new senders in
+ * without a host leg; the way out was the host's: download the stamps, compare, wq_remove_peers (which
+ * builds and uploads a bitmap and waits), wq_ingest_drop_peers_device, the free list, and the uuid text of
+ * every PeerDisconnect made per peer. Here one call finds who leaves and writes everything that hangs on
+ * it, and a second takes the first one's bitmap through WorldMap::remove_peer. Reference:
+ * transport/peer.rs:50-69 (is_stale: now - last_heartbeat > max_duration, strict; WebSocket peers never),
+ * transport/zeromq/outgoing.rs:132-150 (collect the stale set, then remove each),
+ * transport/peer_map.rs:121-141 (remove broadcasts PeerDisconnect with parameter = uuid.to_string()),
+ * processing/thread.rs:124-125 -> WorldMap::remove_peer. An extension like the join; the host definition is
+ * ingest.leave_peers_np and the arithmetic is csrc/leave_ops.hpp.
+ *
+ * wq_ingest_leave_device
+ *   - Walks the live entries of the handle's sender table (wq_ingest_peers_reserve; the live count is the
+ *     device word). An entry with id < n_ids leaves when its id is in leave_ids[n_leave] (the disconnects
+ *     the transport reported) or when it is stale: its bit in pinned_bits is clear (pinned ids are never
+ *     stale: the WebSocket rule), stamp = last_seen[id] != WQ_SEEN_NEVER, now > stamp and
+ *     now - stamp > max_age. A stamp in the future is not stale. Listed ids the table lacks, listed ids
+ *     >= n_ids and duplicates are ignored. A live entry with id >= n_ids is never judged, never stamped
+ *     and sets error bit 2. The table's ids are distinct.
+ *   - WQ_SEEN_NEVER (0xFFFFFFFF) means "not seen yet": the caller initialises last_seen to all ones, and
+ *     the join does not stamp a joiner. A live entry that does not leave and carries it gets
+ *     last_seen[id] = now, so a joiner's clock starts at the first sweep after it joined: at most one sweep
+ *     interval later than the reference's Peer::new_zmq, which starts it at creation. Every leaver's stamp
+ *     is reset to WQ_SEEN_NEVER, so a recycled id starts fresh and never inherits its previous owner's
+ *     stamp. now == WQ_SEEN_NEVER is WQ_E_INVALID.
+ *   - Leavers are listed in table order (uuid ascending), leaver k of n_left in row k of the out arrays,
+ *     each nullable, leave_capacity rows: l_uuid[16 k], l_id[k], l_reason[k] (bit 0 listed, bit 1 stale),
+ *     l_param[36 k ..) = the uuid as lower-case hyphenated text with l_param_offsets[k] = 36 k and the
+ *     entry l_param_offsets[n_left] behind them (leave_capacity + 1 entries): exactly the param /
+ *     param_offsets pair of wq_frames_src, so the PeerDisconnect frames come from wq_frames_build_device
+ *     with no text made on the host.
+ *   - gone_bits[ceil(n_ids / 32)]: one bit per leaver's id, every other bit zero; always written whole
+ *     (also without a reserved table), all zeros on overflow. What wq_remove_peers_device takes.
+ *   - free_out[free_capacity]: the caller's new free list in pop order: the leavers' ids in reverse leave
+ *     order, then free_ids[0 .. n_free) (its free list in pop order, as the join takes it). That is what
+ *     releasing the leavers in leave order leaves. free_out must not overlap free_ids.
+ *   - The sender table loses the leavers by a stable compaction (keys stay ascending) and the live count is
+ *     updated on the device: the next decode no longer resolves them.
+ *   - wq_leave_counters: n_table_before, n_listed (= n_leave), n_listed_found (live entries whose id is
+ *     listed), n_stale (live entries that are stale, listed or not), n_left, n_stamped (clocks started),
+ *     n_table (after), n_free (the free list's length after), overflow, error. n_left is the device word
+ *     wq_remove_peers_device reads as d_count.
+ *   - All or nothing: overflow bit 0: n_left > leave_capacity (looked at only when an l_* array is
+ *     given); bit 1: n_free + n_left > free_capacity (only when free_out is given). With either set no
+ *     stamp, no table entry, no l_* row and no free_out entry is written, gone_bits is zero and the
+ *     counters say what was needed: n_left is what would have left, n_stamped 0, n_table and n_free as
+ *     before the call.
+ *   - error bit 1: the handle has no reserved table; the call is then a no-op: gone_bits is zeroed and the
+ *     counters hold n_listed, n_free as given and error bit 1, everything else 0. error bit 2 above.
+ *   - Asynchronous on the handle's stream, nothing read back, deterministic byte for byte: no lane owns a
+ *     peer, every placement comes from one scan, and the only atomics are integer ORs into the bitmaps and
+ *     integer adds / ORs into the counters. Scratch lives in the handle, grow-only: 21 bytes per reserved
+ *     table entry (20 of them the table's second buffer, shared with the join), 12 per 64 entries and 4
+ *     per 32 ids; a steady-state call does no hipMalloc. Every table pass has one lane per reserved entry
+ *     and reads the live count on the device.
+ *   - WQ_E_INVALID, nothing launched: a null handle, in or out; a null last_seen with n_ids > 0; n_leave > 0
+ *     without leave_ids; n_free > 0 without free_ids; n_ids, n_leave or n_free >= 2^32 - 1; now ==
+ *     WQ_SEEN_NEVER.
+ *   - A multi-GPU handle runs the call on its own stream with the arrays on devices[0], as the join.
+ * wq_remove_peers_device
+ *   - wq_remove_peers for the ids < n_ids whose bit is set in d_bits[ceil(n_ids / 32)]: every world, in
+ *     place, the same kernel on the same pass, with the same results. Follow state, peer positions and
+ *     last_seen are left alone, as wq_remove_peers leaves them.
+ *   - No bitmap is built on the host, nothing is uploaded and the call does not wait for the stream;
+ *     d_bits (and *d_count) must stay unchanged until the stream has passed the call. A batch still in
+ *     flight is folded in first, as in wq_remove_peers; an empty table launches nothing.
+ *   - d_count (nullable): a device u64, the number of set bits or any value that is 0 only when no bit
+ *     is set (wq_leave_counters.n_left). With *d_count == 0 every block returns before it touches the
+ *     table.
+ *   - The host cannot know whether a bit is set, so the call invalidates what wq_remove_peers
+ *     invalidates (the table generation, the compact headers, the sorted state) whether or not anybody is
+ *     removed. It belongs at the sweep interval, not in every tick; the reference sweeps on a timer too.
+ *   - WQ_E_INVALID: a null handle; a null d_bits with n_ids > 0; a multi-GPU handle (its shards take the
+ *     ids on the host: wq_remove_peers). */
+#define WQ_SEEN_NEVER 0xFFFFFFFFu    /* last_seen: not seen yet */
+
+typedef struct wq_leave_in {         /* device pointers unless noted */
+    uint32_t*       last_seen;       /* [n_ids] required with n_ids > 0; written */
+    const uint32_t* pinned_bits;     /* [ceil(n_ids / 32)] nullable: ids that are never stale */
+    const uint32_t* leave_ids;       /* [n_leave] nullable with n_leave 0 */
+    const uint32_t* free_ids;        /* [n_free] nullable with n_free 0: the free list in pop order */
+    uint32_t        n_ids, now, max_age, n_leave, n_free, pad_;   /* host values */
+} wq_leave_in;               /* 56 bytes */
+
+typedef struct wq_leave_out {        /* device pointers, each nullable */
+    uint8_t*  l_uuid;                /* [16 leave_capacity] */
+    uint32_t* l_id;                  /* [leave_capacity] */
+    uint8_t*  l_reason;              /* [leave_capacity] */
+    uint8_t*  l_param;               /* [36 leave_capacity] */
+    uint64_t* l_param_offsets;       /* [leave_capacity + 1] */
+    uint32_t* gone_bits;             /* [ceil(n_ids / 32)] */
+    uint32_t* free_out;              /* [free_capacity] */
+    uint32_t  leave_capacity, free_capacity;
+} wq_leave_out;              /* 64 bytes */
+
+typedef struct wq_leave_counters {
+    uint64_t n_table_before, n_listed, n_listed_found, n_stale;
+    uint64_t n_left, n_stamped, n_table, n_free, overflow, error;
+} wq_leave_counters;         /* 80 bytes */
+
+int wq_ingest_leave_device(wq_router* h, const wq_leave_in* in, const wq_leave_out* out,
+                           wq_leave_counters* d_counters /* nullable */);
+int wq_remove_peers_device(wq_router* h, const uint32_t* d_bits, uint32_t n_ids, const uint64_t* d_count /* nullable */);
+
 /* ---- record store: RecordCreate / RecordRead / RecordDelete ----
  * The reference sends these three instructions to DatabaseClient (database/client.rs) and PostgreSQL.
  * Here the spatial index of the records lives in the handle: one row per stored record holding its

@@ -181,6 +181,31 @@ class JoinOut(ctypes.Structure):  # struct wq_join_out: device pointers, each nu
 assert ctypes.sizeof(JoinIn) == 64 and ctypes.sizeof(JoinOut) == 32 and JOIN_COUNTERS_DTYPE.itemsize == 80
 
 
+# ---- ingest leaves (wq_ingest_leave_device, wq_remove_peers_device) ----
+SEEN_NEVER = 0xFFFFFFFF                                         # WQ_SEEN_NEVER: last_seen of an id not seen yet
+LEAVE_LISTED, LEAVE_STALE = 1, 2                                # wq_leave_out.l_reason bits 0 and 1
+LEAVE_ERROR_NO_TABLE, LEAVE_ERROR_ID_RANGE = 2, 4               # wq_leave_counters.error bits 1 and 2
+LEAVE_OVERFLOW_OUT, LEAVE_OVERFLOW_FREE = 1, 2                  # wq_leave_counters.overflow bits 0 and 1
+LEAVE_TEXT = 36                                                 # bytes of a uuid's text in l_param
+# struct wq_leave_counters: 80 bytes
+LEAVE_COUNTERS_DTYPE = np.dtype([(k, np.uint64) for k in ("n_table_before", "n_listed", "n_listed_found", "n_stale", "n_left",
+                                                          "n_stamped", "n_table", "n_free", "overflow", "error")])
+
+
+class LeaveIn(ctypes.Structure):  # struct wq_leave_in: device pointers and host values; last_seen is written
+    _fields_ = [(k, ctypes.c_void_p) for k in ("last_seen", "pinned_bits", "leave_ids", "free_ids")] + \
+               [(k, ctypes.c_uint32) for k in ("n_ids", "now", "max_age", "n_leave", "n_free", "pad_")]
+
+
+class LeaveOut(ctypes.Structure):  # struct wq_leave_out: device pointers, each nullable
+    _fields_ = [(k, ctypes.c_void_p) for k in ("l_uuid", "l_id", "l_reason", "l_param", "l_param_offsets", "gone_bits",
+                                               "free_out")] + \
+               [("leave_capacity", ctypes.c_uint32), ("free_capacity", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(LeaveIn) == 56 and ctypes.sizeof(LeaveOut) == 64 and LEAVE_COUNTERS_DTYPE.itemsize == 80
+
+
 # ---- record dispatch (wq_records_dispatch_device) ----
 # WQ_RCLS_*: the class of a listed frame, in the order of wq_recdisp_counters' per-class counts
 RCLS_SKIP, RCLS_APPLY, RCLS_READ, RCLS_READ_DROPPED, RCLS_READ_DEFERRED = range(5)

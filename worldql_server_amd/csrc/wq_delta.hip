@@ -1072,8 +1072,13 @@ __device__ __forceinline__ bool removed(const RemoveSet& rs, uint32_t w, uint32_
 }
 
 __global__ __launch_bounds__(kBlock) void k_remove_peers(DeltaTable tb, const Slot* __restrict__ slots,
-                                                         uint64_t scap, RemoveSet rs, uint64_t* part) {
+                                                         uint64_t scap, RemoveSet rs, uint64_t* part,
+                                                         const uint64_t* __restrict__ skip_if_zero) {
     __shared__ unsigned long long acc[2];
+    if (skip_if_zero && *skip_if_zero == 0) {  // block-uniform: nobody is removed, the table is not touched
+        if (threadIdx.x < 2) part[2ull * blockIdx.x + threadIdx.x] = 0;
+        return;
+    }
     if (threadIdx.x < 2) acc[threadIdx.x] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63, gl = threadIdx.x & (kG - 1), grp = threadIdx.x / kG;
@@ -1415,9 +1420,36 @@ int table_resolve(wq_router* h, bool blocking) {
     return table_rebuild_batch(h, pd.n);
 }
 
-int table_remove_peers_inplace(wq_router* h, const uint64_t* keys, size_t n_rm) {
+// The pass itself on a RemoveSet whose arrays are on the device (asynchronous).
+static int remove_peers_launch(wq_router* h, const RemoveSet& rs, const uint64_t* d_count) {
     DeltaWs& d = h->dws;
     Table& t = h->tab;
+    hipStream_t s = h->stream;
+    WQ_ALLOC(h, d.part, (uint64_t)kGroupGrid * 32);
+    if (!d.dstat.p) {
+        WQ_ALLOC(h, d.dstat, 16);
+        WQ_HIP(h, hipMemsetAsync(d.dstat.p, 0, 16, s));
+    }
+    DeltaTable tb{t.recs.as<Record>(), t.rclaim.as<uint32_t>(), t.rec_cap - 1, t.rec_shift, h->hash_mask,
+                  t.list.as<uint32_t>()};
+    const uint64_t D = t.rec_cap + t.cap;
+    const uint32_t ng = (uint32_t)std::min<uint64_t>((D + kGroups - 1) / kGroups, kGroupGrid);
+    hipLaunchKernelGGL(k_remove_peers, dim3(ng), dim3(kBlock), 0, s, tb, t.slots.as<Slot>(), t.cap, rs,
+                       d.part.as<uint64_t>(), d_count);
+    hipLaunchKernelGGL(k_delta_stats, dim3(1), dim3(kBlock), 0, s, d.part.as<uint64_t>(), ng, d.dstat.as<uint64_t>());
+    WQ_HIP(h, hipGetLastError());
+    h->dstat_pending = true;
+    h->st_stale = true;
+    h->any_stale = true;
+    return WQ_OK;
+}
+
+int table_remove_peers_bits(wq_router* h, const uint32_t* d_bits, uint32_t n_ids, const uint64_t* d_count) {
+    return remove_peers_launch(h, RemoveSet{d_bits, n_ids, nullptr, 0}, d_count);
+}
+
+int table_remove_peers_inplace(wq_router* h, const uint64_t* keys, size_t n_rm) {
+    DeltaWs& d = h->dws;
     hipStream_t s = h->stream;
     // split: (WQ_WORLD_INVALID, peer) = every world -> bitmap; the rest stay sorted keys
     size_t n_all = 0;
@@ -1446,22 +1478,7 @@ int table_remove_peers_inplace(wq_router* h, const uint64_t* keys, size_t n_rm) 
         WQ_HIP(h, hipMemcpyAsync(h->key32_b.p, keys, n_one * 8, hipMemcpyHostToDevice, s));
         rs.keys = h->key32_b.as<uint64_t>();
     }
-    WQ_ALLOC(h, d.part, (uint64_t)kGroupGrid * 32);
-    if (!d.dstat.p) {
-        WQ_ALLOC(h, d.dstat, 16);
-        WQ_HIP(h, hipMemsetAsync(d.dstat.p, 0, 16, s));
-    }
-    DeltaTable tb{t.recs.as<Record>(), t.rclaim.as<uint32_t>(), t.rec_cap - 1, t.rec_shift, h->hash_mask,
-                  t.list.as<uint32_t>()};
-    const uint64_t D = t.rec_cap + t.cap;
-    const uint32_t ng = (uint32_t)std::min<uint64_t>((D + kGroups - 1) / kGroups, kGroupGrid);
-    hipLaunchKernelGGL(k_remove_peers, dim3(ng), dim3(kBlock), 0, s, tb, t.slots.as<Slot>(), t.cap, rs,
-                       d.part.as<uint64_t>());
-    hipLaunchKernelGGL(k_delta_stats, dim3(1), dim3(kBlock), 0, s, d.part.as<uint64_t>(), ng, d.dstat.as<uint64_t>());
-    WQ_HIP(h, hipGetLastError());
-    h->dstat_pending = true;
-    h->st_stale = true;
-    h->any_stale = true;
+    if (int rc = remove_peers_launch(h, rs, nullptr)) return rc;
     // the host arrays above are read by copies still in flight
     WQ_HIP(h, hipStreamSynchronize(s));
     return WQ_OK;

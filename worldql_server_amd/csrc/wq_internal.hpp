@@ -305,6 +305,9 @@ struct wq_router {
     // and the control block between the passes.
     wq::DevBuf ing_live, join_ws, join_tab, join_ctrl;
     uint32_t ing_cap = 0;
+    // ingest leaves (wq_leave.hip): a call's scratch (per reserved table entry and per 32 ids) and the
+    // control block between the passes; the table's second buffer is join_tab
+    wq::DevBuf leave_ws, leave_ctrl;
     // ingest dispatch (wq_dispatch.hip): per frame its class between the passes; one DspSum per 1,024
     // frames and the total behind them
     wq::DevBuf dsp_cls, dsp_sum;
@@ -388,6 +391,9 @@ int launch_op_owner(wq_router* h, const wq_op* d_ops, size_t n, uint32_t G, uint
 int table_apply_segment(wq_router* h, const wq_op* ops, size_t n, bool on_device = false);
 // keys: sorted unique (world << 32 | peer); world == WQ_WORLD_INVALID removes the peer everywhere.
 int table_remove_peers(wq_router* h, const uint64_t* keys_sorted_unique, size_t n);
+// The same for the peers whose bit is set in a device bitmap of n_ids bits, removed from every world;
+// nothing is uploaded or waited for. d_count (nullable): a device word, 0 = no bit is set.
+int table_remove_peers_device(wq_router* h, const uint32_t* d_bits, uint32_t n_ids, const uint64_t* d_count);
 int table_rebuild_derived(wq_router* h);
 // wq_delta.hip. Applies n subscribe / unsubscribe ops (h->cur_ops) to the records and lists in
 // place; *applied = false (and nothing changed) when the batch needs the full rebuild.
@@ -395,6 +401,9 @@ int table_apply_delta(wq_router* h, size_t n, bool* applied);
 // REMOVE_PEER in place: keys sorted unique (world << 32 | peer), world WQ_WORLD_INVALID = every
 // world; one pass over every cube's list (wq_delta.hip).
 int table_remove_peers_inplace(wq_router* h, const uint64_t* keys, size_t n);
+// The same pass for a bitmap already on the device (n_ids bits): asynchronous, nothing uploaded. With
+// d_count given and *d_count == 0 every block returns before it touches the table.
+int table_remove_peers_bits(wq_router* h, const uint32_t* d_bits, uint32_t n_ids, const uint64_t* d_count);
 // Folds the device-side entry / live-cube deltas of incremental batches into st.n / tab.n_cubes
 // (synchronises the stream).
 int table_sync_delta_stats(wq_router* h);
@@ -466,6 +475,10 @@ int launch_ingest_join(wq_router* h, const wq_join_in* in, size_t n_frames, cons
                        wq_join_counters* d_counters);
 int launch_ingest_drop(wq_router* h, const uint32_t* d_ids, size_t n, wq_join_counters* d_counters);
 void join_release(wq_router* h);
+// wq_leave.hip: the leaves on device arrays (asynchronous; arguments validated) and the release of their
+// scratch.
+int launch_ingest_leave(wq_router* h, const wq_leave_in* in, const wq_leave_out* out, wq_leave_counters* d_counters);
+void leave_release(wq_router* h);
 // wq_dispatch.hip: the dispatch on device arrays (asynchronous) and the release of its scratch.
 int launch_ingest_dispatch(wq_router* h, const wq_dispatch_in* in, size_t n_frames, const wq_dispatch_out* out,
                            wq_dispatch_counters* d_counters);

@@ -131,6 +131,7 @@ int wq_router_destroy(wq_router* h) {
     frames_release(h);
     ingest_release(h);
     join_release(h);
+    leave_release(h);
     dispatch_release(h);
     recdispatch_release(h);
     slab_release(h);
@@ -859,6 +860,28 @@ int wq_ingest_drop_peers_device(wq_router* h, const uint32_t* d_ids, size_t n, w
     if (n >= 0xFFFFFFFFull) return set_error(h, WQ_E_INVALID, "ingest_drop_peers: n must be < 2^32 - 1");
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_ingest_drop(h, d_ids, n, d_counters);
+}
+
+int wq_ingest_leave_device(wq_router* h, const wq_leave_in* in, const wq_leave_out* out, wq_leave_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!in || !out) return set_error(h, WQ_E_INVALID, "ingest_leave: in or out is null");
+    if (in->n_ids && !in->last_seen) return set_error(h, WQ_E_INVALID, "ingest_leave: last_seen is null");
+    if (in->n_leave && !in->leave_ids) return set_error(h, WQ_E_INVALID, "ingest_leave: n_leave without leave_ids");
+    if (in->n_free && !in->free_ids) return set_error(h, WQ_E_INVALID, "ingest_leave: n_free without free_ids");
+    if (in->n_ids == 0xFFFFFFFFu || in->n_leave == 0xFFFFFFFFu || in->n_free == 0xFFFFFFFFu)
+        return set_error(h, WQ_E_INVALID, "ingest_leave: n_ids, n_leave and n_free must be < 2^32 - 1");
+    if (in->now == WQ_SEEN_NEVER) return set_error(h, WQ_E_INVALID, "ingest_leave: now must not be WQ_SEEN_NEVER");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_ingest_leave(h, in, out, d_counters);
+}
+
+int wq_remove_peers_device(wq_router* h, const uint32_t* d_bits, uint32_t n_ids, const uint64_t* d_count) {
+    if (!h) return WQ_E_INVALID;
+    if (n_ids && !d_bits) return set_error(h, WQ_E_INVALID, "remove_peers_device: d_bits is null");
+    if (h->multi)
+        return set_error(h, WQ_E_INVALID, "remove_peers_device: a multi-GPU handle takes the ids on the host (wq_remove_peers)");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return table_remove_peers_device(h, d_bits, n_ids, d_count);
 }
 
 int wq_records_dispatch_device(wq_router* h, const wq_recdisp_in* in, const wq_recdisp_out* out,

@@ -436,6 +436,16 @@ int table_remove_peers(wq_router* h, const uint64_t* keys, size_t n_rm) {
     return table_remove_peers_inplace(h, keys, n_rm);
 }
 
+int table_remove_peers_device(wq_router* h, const uint32_t* d_bits, uint32_t n_ids, const uint64_t* d_count) {
+    // the same prelude: how many bits are set is only known on the device, so the generation and the
+    // compact headers go as if one were
+    if (int rc = table_resolve(h, true)) return rc;
+    if (n_ids == 0 || (h->st.n == 0 && !h->dstat_pending)) return WQ_OK;
+    h->table_gen++;
+    h->tab.hdr_ok = false;
+    return table_remove_peers_bits(h, d_bits, n_ids, d_count);
+}
+
 // Compact headers: every occupied record (ext != 0; emptied cubes keep theirs) claims the first free
 // slot of its probe run in the header table by a CAS on the header's ext word (each cube is inserted
 // once, so a claimed slot is simply passed), then writes {pk, count, list_off | sig, record slot}.

@@ -372,6 +372,94 @@ def join_counters(raw) -> dict:
     return {k: int(c[k]) for k in abi.JOIN_COUNTERS_DTYPE.names}
 
 
+# ---- ingest leaves: stale and disconnected senders leave (wq_ingest_leave_device) ----
+def id_bits(ids, n_ids: int) -> np.ndarray:
+    """The u32 bitmap of ceil(n_ids / 32) words with the bits of `ids` set: pinned_bits, gone_bits."""
+    bits = np.zeros((int(n_ids) + 31) // 32, np.uint32)
+    for i in ids:
+        bits[int(i) >> 5] |= np.uint32(1 << (int(i) & 31))
+    return bits
+
+
+def leave_peers_np(table_uuids, table_ids, last_seen, now, max_age, pinned, leave_ids, free, leave_capacity, free_capacity,
+                   reserved=True):
+    """The definition of wq_ingest_leave_device: a plain loop over the sender table (uuids ascending, ids),
+    one entry at a time. last_seen: the u32 stamps, one per id (n_ids of them); pinned: a u32 bitmap as
+    id_bits makes it, or None; leave_ids: the listed disconnects; free: the free list in pop order;
+    leave_capacity / free_capacity None: the l_* arrays / free_out are not given. An entry with id < n_ids
+    leaves when its id is listed (reason bit 0) or its stamp is stale (bit 1): not pinned, not SEEN_NEVER,
+    now > stamp and now - stamp > max_age. An entry that stays and carries SEEN_NEVER is stamped `now`; a
+    leaver's stamp goes back to SEEN_NEVER. Returns a dict of l_uuid u8[k, 16], l_id u32[k], l_reason u8[k],
+    l_param u8[36 k], l_param_offsets u64[k + 1], gone_bits, free_out (the leavers' ids in reverse leave
+    order, then free), last_seen (a copy), table (uuids, ids) and counters (abi.LEAVE_COUNTERS_DTYPE's
+    fields). With an overflow bit set or without a reserved table nothing changes, the rows and free_out are
+    empty and gone_bits is zero."""
+    rows = uuid_rows(table_uuids if table_uuids is not None else [])
+    ids = np.arange(len(rows), dtype=np.uint32) if table_ids is None else np.asarray(table_ids, dtype=np.uint32)
+    seen = np.array(last_seen, np.uint32, copy=True).reshape(-1)
+    n_ids, now, max_age = len(seen), int(now), int(max_age)
+    if not 0 <= now < abi.SEEN_NEVER:
+        raise ValueError("now must be below SEEN_NEVER")
+    listed = {int(v) for v in (leave_ids if leave_ids is not None else [])}
+    n_listed = len(leave_ids) if leave_ids is not None else 0
+    free = [int(v) for v in (free if free is not None else [])]
+    pin = None if pinned is None else np.asarray(pinned, np.uint32)
+    cnt = {k: 0 for k in abi.LEAVE_COUNTERS_DTYPE.names}
+    cnt.update(n_listed=n_listed, n_free=len(free))
+    empty = dict(l_uuid=np.zeros((0, 16), np.uint8), l_id=np.zeros(0, np.uint32), l_reason=np.zeros(0, np.uint8),
+                 l_param=np.zeros(0, np.uint8), l_param_offsets=np.zeros(0, np.uint64), gone_bits=id_bits([], n_ids),
+                 free_out=np.zeros(0, np.uint32))
+    table = (rows.copy(), ids.copy())
+    if not reserved:
+        cnt["error"] = abi.LEAVE_ERROR_NO_TABLE
+        return dict(last_seen=seen, table=table, counters=cnt, **empty)
+    leavers, reasons, stamp_now, error, n_found, n_stale = [], [], [], 0, 0, 0
+    for e in range(len(rows)):
+        i = int(ids[e])
+        if i >= n_ids:
+            error |= abi.LEAVE_ERROR_ID_RANGE
+            continue
+        stamp = int(seen[i])
+        is_pinned = pin is not None and (int(pin[i >> 5]) >> (i & 31)) & 1
+        reason = abi.LEAVE_LISTED if i in listed else 0
+        if not is_pinned and stamp != abi.SEEN_NEVER and now > stamp and now - stamp > max_age:
+            reason |= abi.LEAVE_STALE
+        n_found += bool(reason & abi.LEAVE_LISTED)
+        n_stale += bool(reason & abi.LEAVE_STALE)
+        if reason:
+            leavers.append(e)
+            reasons.append(reason)
+        elif stamp == abi.SEEN_NEVER:
+            stamp_now.append(i)
+    k = len(leavers)
+    overflow = (abi.LEAVE_OVERFLOW_OUT if leave_capacity is not None and k > int(leave_capacity) else 0) | \
+               (abi.LEAVE_OVERFLOW_FREE if free_capacity is not None and len(free) + k > int(free_capacity) else 0)
+    cnt.update(n_table_before=len(rows), n_listed_found=n_found, n_stale=n_stale, n_left=k, n_table=len(rows), overflow=overflow,
+               error=error)
+    if overflow:
+        return dict(last_seen=seen, table=table, counters=cnt, **empty)
+    l_id = ids[leavers].astype(np.uint32)
+    for i in stamp_now:
+        seen[i] = now
+    for i in l_id:
+        seen[int(i)] = abi.SEEN_NEVER
+    keep = np.ones(len(rows), bool)
+    keep[leavers] = False
+    text = "".join(str(_uuid.UUID(bytes=rows[e].tobytes())) for e in leavers).encode()
+    cnt.update(n_stamped=len(stamp_now), n_table=len(rows) - k, n_free=len(free) + k)
+    return dict(l_uuid=rows[leavers].reshape(-1, 16).copy(), l_id=l_id, l_reason=np.array(reasons, np.uint8),
+                l_param=np.frombuffer(text, np.uint8).copy(),
+                l_param_offsets=np.arange(k + 1, dtype=np.uint64) * np.uint64(abi.LEAVE_TEXT),
+                gone_bits=id_bits(l_id, n_ids), free_out=np.array([int(i) for i in l_id[::-1]] + free, np.uint32),
+                last_seen=seen, table=(rows[keep].copy(), ids[keep].copy()), counters=cnt)
+
+
+def leave_counters(raw) -> dict:
+    """abi.LEAVE_COUNTERS_DTYPE bytes as leave_peers_np's counters dict."""
+    c = np.asarray(raw).view(np.uint8)[:abi.LEAVE_COUNTERS_DTYPE.itemsize].view(abi.LEAVE_COUNTERS_DTYPE)[0]
+    return {k: int(c[k]) for k in abi.LEAVE_COUNTERS_DTYPE.names}
+
+
 # ---- the record dispatch: the record frames of a tick to store ops and queries (wq_records_dispatch_device) ----
 _VT_RECORDS = 14                                              # Message.records' vtable slot
 _VT_REC_UUID, _VT_REC_POS, _VT_REC_WORLD, _VT_REC_DATA, _VT_REC_FLEX = 4, 6, 8, 10, 12   # Record's slots
@@ -826,6 +914,64 @@ class IngestTick:
                     j_uuid=raw[8 * J:8 * J + 16 * k].reshape(k, 16).copy(),
                     sender=self.buf["sender"][:4 * n].cpu().numpy().view(np.uint32),
                     flags=self.buf["flags"][:n].cpu().numpy())
+
+    # ---- the leaves: the sweep between ticks (wq_ingest_leave_device, then wq_remove_peers_device) ----
+    _LSPEC = dict(l_uuid=16, l_id=4, l_reason=1, l_param=abi.LEAVE_TEXT)
+
+    def leave(self, last_seen, now: int, max_age: int, pinned_bits=None, leave_ids=None, free_ids=None,
+              leave_capacity: int | None = None, free_capacity: int | None = None, remove: bool = True) -> "IngestTick":
+        """Enqueues wq_ingest_leave_device and, with `remove`, wq_remove_peers_device on its bitmap and its
+        n_left, back to back on the handle's stream; nothing is read back. last_seen: the uint32 device tensor
+        the dispatch stamps (one entry per id, initialised to abi.SEEN_NEVER); pinned_bits, leave_ids, free_ids:
+        uint32 device tensors or None. The outputs stay on the device, grow-only: `lbuf` holds l_uuid, l_id,
+        l_reason, l_param, l_param_offsets (leave_capacity rows, default the ids' count), gone_bits and free_out
+        (free_capacity entries, default the free list's length plus leave_capacity), `leave_counters_dev` the
+        counters. l_param / l_param_offsets are what Router.build_frames_device takes for the PeerDisconnect
+        frames. read_leave() fetches everything."""
+        import torch
+        n_ids = last_seen.numel()
+        n_free = 0 if free_ids is None else free_ids.numel()
+        n_leave = 0 if leave_ids is None else leave_ids.numel()
+        lc = n_ids if leave_capacity is None else leave_capacity
+        fc = n_free + lc if free_capacity is None else free_capacity
+        words = (n_ids + 31) // 32
+        need = dict(l_uuid=16 * lc, l_id=4 * lc, l_reason=lc, l_param=abi.LEAVE_TEXT * lc, l_param_offsets=8 * (lc + 1),
+                    gone_bits=4 * words, free_out=4 * fc)
+        if not hasattr(self, "lbuf"):
+            self.lbuf = {}
+            self.leave_counters_dev = torch.empty(abi.LEAVE_COUNTERS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        for k, b in need.items():
+            if k not in self.lbuf or self.lbuf[k].numel() < b:
+                # empty, not zeros: a fill would run on torch's stream, beside the call on the handle's
+                self.lbuf[k] = torch.empty(max(2 * b, 8), dtype=torch.uint8, device=self.device)
+        ptr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+        self.lv_n_ids, self.lv_capacity, self.lv_free_capacity = n_ids, lc, fc
+        self.lv_in = abi.LeaveIn(last_seen=ptr(last_seen), pinned_bits=ptr(pinned_bits), leave_ids=ptr(leave_ids),
+                                 free_ids=ptr(free_ids), n_ids=n_ids, now=now, max_age=max_age, n_leave=n_leave, n_free=n_free)
+        self.lv_out = abi.LeaveOut(**{k: t.data_ptr() for k, t in self.lbuf.items()}, leave_capacity=lc, free_capacity=fc)
+        self.lv_last_seen = last_seen
+        cptr = self.leave_counters_dev.data_ptr()
+        self.router.leave_peers_device(self.lv_in, self.lv_out, cptr)
+        if remove:
+            self.router.remove_peers_device(self.lbuf["gone_bits"].data_ptr(), n_ids,
+                                            cptr + abi.LEAVE_COUNTERS_DTYPE.fields["n_left"][1])
+        return self
+
+    def read_leave(self) -> dict:
+        """The last leave()'s outputs and counters as numpy arrays shaped like leave_peers_np's (synchronizes;
+        for tests, and for the host's PeerIds.release_ids after a sweep with leavers)."""
+        import torch
+        torch.cuda.synchronize()
+        cnt = leave_counters(self.leave_counters_dev.cpu().numpy())
+        done = not cnt["overflow"] and not cnt["error"] & abi.LEAVE_ERROR_NO_TABLE
+        k = cnt["n_left"] if done else 0
+        raw = {name: self.lbuf[name][:k * w].cpu().numpy() for name, w in self._LSPEC.items()}
+        return dict(counters=cnt, l_uuid=raw["l_uuid"].reshape(k, 16), l_id=raw["l_id"].view(np.uint32), l_reason=raw["l_reason"],
+                    l_param=raw["l_param"],
+                    l_param_offsets=self.lbuf["l_param_offsets"][:8 * (k + 1) if done else 0].cpu().numpy().view(np.uint64),
+                    gone_bits=self.lbuf["gone_bits"][:4 * ((self.lv_n_ids + 31) // 32)].cpu().numpy().view(np.uint32),
+                    free_out=self.lbuf["free_out"][:4 * cnt["n_free"] if done else 0].cpu().numpy().view(np.uint32),
+                    last_seen=self.lv_last_seen.cpu().numpy().view(np.uint32).reshape(-1))
 
     def _read_ctrl(self):
         """The counters and the run table: one copy for tables of up to RUNS_FIRST_READ entries. Waits for

@@ -92,6 +92,8 @@ def load_library(build_if_missing: bool = True):
         "wq_ingest_peers_reserve": ([vp, sz], i32),
         "wq_ingest_join_device": ([vp, ctypes.POINTER(abi.JoinIn), sz, ctypes.POINTER(abi.JoinOut), vp], i32),
         "wq_ingest_drop_peers_device": ([vp, vp, sz, vp], i32),
+        "wq_ingest_leave_device": ([vp, ctypes.POINTER(abi.LeaveIn), ctypes.POINTER(abi.LeaveOut), vp], i32),
+        "wq_remove_peers_device": ([vp, vp, ctypes.c_uint32, vp], i32),
         "wq_ingest_peers_read": ([vp, vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_csr_diff_device": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp], i32),
         "wq_csr_diff": ([vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz),
@@ -556,6 +558,26 @@ class Router:
         if n.value:
             self._check(self.lib.wq_ingest_peers_read(self.h, u.ctypes.data, i.ctypes.data, n.value, ctypes.byref(n)))
         return u, i
+
+    # ---- ingest leaves (include/wq_router.h, "ingest leaves"; host definition: ingest.leave_peers_np) ----
+    def leave_peers_device(self, src: "abi.LeaveIn", out: "abi.LeaveOut", counters_ptr: int | None = None) -> None:
+        """wq_ingest_leave_device: the sweep. Every live sender-table entry whose id is listed in
+        src.leave_ids or whose stamp in src.last_seen is stale (now - stamp > max_age, strict; never a pinned
+        id, a stamp ahead or abi.SEEN_NEVER) leaves: `out` (abi.LeaveOut, each nullable) takes the leavers in
+        uuid order with their uuid text as build_frames_device's param / param_offsets, the bitmap
+        remove_peers_device takes and the new free list; the stamps of the leavers are reset, the clocks of
+        new entries start, and the table is compacted. All or nothing on overflow. Asynchronous on the
+        handle's stream; the counters (abi.LEAVE_COUNTERS_DTYPE) stay where counters_ptr points."""
+        self._check(self.lib.wq_ingest_leave_device(self.h, ctypes.byref(src) if src is not None else None,
+                                                    ctypes.byref(out) if out is not None else None, counters_ptr or None))
+
+    def remove_peers_device(self, bits_ptr: int | None, n_ids: int, count_ptr: int | None = None) -> None:
+        """wq_remove_peers_device: remove_peers for the ids < n_ids whose bit is set in the device bitmap at
+        bits_ptr (u32 words), with nothing built, uploaded or waited for on the host. count_ptr: a device u64
+        (the leave's n_left); when it holds 0 the kernel returns before it touches the table. Invalidates what
+        remove_peers invalidates whether or not a bit is set: a call for the sweep interval, not every tick.
+        Single-GPU handles only."""
+        self._check(self.lib.wq_remove_peers_device(self.h, bits_ptr or None, n_ids, count_ptr or None))
 
     def records_dispatch_device(self, src: "abi.RecDispatchIn", out: "abi.RecDispatchOut",
                                 counters_ptr: int | None = None) -> None:

@@ -113,6 +113,19 @@ class PeerIds:
                 self._peers.append(p)
             self._ids[p] = pid
 
+    def release_ids(self, peers, ids) -> None:
+        """Forgets the peers the device removed (wq_ingest_leave_device's l_uuid / l_id, in leave order): the
+        counterpart of `adopt`. Releases in the given order, so `free_in_pop_order` then equals the call's
+        free_out. A peer that does not hold the id given for it, or occurs twice, raises ValueError and
+        leaves the map as it was."""
+        peers, ids = list(peers), [int(i) for i in ids]
+        if len(peers) != len(ids):
+            raise ValueError("release_ids: one id per peer")
+        if len(set(peers)) != len(peers) or any(self._ids.get(p) != i for p, i in zip(peers, ids)):
+            raise ValueError("release_ids: a peer that does not hold the id given for it, or occurs twice")
+        for p in peers:
+            self.release(p)
+
     @property
     def high_water(self) -> int:
         """Ids ever handed out at once: per-peer device arrays need this many entries."""
