@@ -611,6 +611,87 @@ int wq_peer_major_device(wq_router* h, const uint32_t* d_offsets, const uint32_t
                          size_t n_pairs, const uint32_t* d_connected, uint32_t n_peers,
                          uint32_t* d_peer_offsets, uint32_t* d_msgs_out);
 
+/* ---- tick sends: one per-peer frame list from all of a tick's read runs ----
+ * A received tick is routed run by run (wq_ingest_dispatch_device): every read run leaves a CSR region
+ * for its LocalMessage rows, one for its GlobalMessage rows, or both, and row k of a region is frame
+ * l_src[l_begin + k] or g_src[g_begin + k] of the tick. wq_peer_major_device transposes one CSR and
+ * names rows; this call transposes all regions of a tick at once and names frames: for every peer the
+ * received frames it must be sent, ascending by frame index — the order in which the reference's
+ * sequential loop (PeerMap::broadcast_to per message, in arrival order) would have sent them, whatever
+ * run or kind a frame came from. Its output is what wq_peer_budget*_device, wq_peer_rotate_device and
+ * wq_peer_pack_device take, with the tick's received frames as the frames.
+ *
+ * Regions (a HOST array, validated and copied before the call returns)
+ *   - The element space is the regions' [0, capacity) laid end to end in region order; n_elems is its
+ *     length, the sum of the capacities. Region g's elements are d_peers[peers_at .. peers_at + capacity).
+ *   - Inside a region a row and its clamping are wq_peer_major_device's with n_pairs = capacity, on the
+ *     region's own n_rows + 1 offsets d_offsets[off_at ..] (region-local, as a route call writes them).
+ *     off_at == WQ_SEND_UNIT_ROWS: row r is element r, for r < min(n_rows, capacity), and d_offsets is
+ *     not read. An element no row covers belongs to nobody. d_offsets is not read for n_rows == 0.
+ *   - The frame of an element of row r is frame_base + (src_at == WQ_SEND_NO_SRC ? r :
+ *     d_src[src_sel][src_at + r]), computed in 64 bits. Nothing assumes that the src entries ascend, and
+ *     the same frame in two rows or two regions is no error: the element is kept twice.
+ *   - A region with n_rows == 0 or capacity == 0 is legal and empty.
+ * Drops and errors (wq_tick_sends_counters.error)
+ *   - An element whose frame is >= n_frames is dropped and counted in n_drop_frame; error bit 1.
+ *   - Of the others, an element whose peer is >= n_peers or not set in d_connected (as
+ *     wq_peer_major_device; NULL = every peer connected) is dropped and counted in n_drop_peer.
+ *   - A cut route call is a legal input: its offsets reach past `capacity`. It sets error bit 0, and so do
+ *     descending offsets; for those the result is well formed but unspecified, as in wq_peer_major_device.
+ *   - n_covered = n_kept + n_drop_peer + n_drop_frame: the elements a row covers.
+ * Outputs
+ *   - d_frames_out[d_peer_offsets[p] .. d_peer_offsets[p + 1]) holds peer p's frames ascending by frame
+ *     index, equal frames in element order. d_peer_offsets[n_peers + 1] is always written in full.
+ *   - All n_elems words of d_frames_out are written on every call: the d_peer_offsets[n_peers] kept ones,
+ *     then zeros. Nothing is written outside the two arrays and the counters, and two calls on the same
+ *     input give the same bytes.
+ * Execution
+ *   - Asynchronous on the handle's stream; nothing is read back. Scratch lives in the handle, grow-only
+ *     (8 or 12 bytes per element, the sort's, 44 bytes per region): a steady-state call does no hipMalloc.
+ *     The regions go through a pinned buffer of the handle's; the call waits for the previous call's copy
+ *     out of that buffer, not for the stream. `regions` is free to reuse when the call returns.
+ *   - Like wq_peer_major_device the call needs only a stream and scratch: a multi-GPU handle runs it on
+ *     its own stream with the arrays on devices[0].
+ * WQ_E_INVALID, with nothing launched and a wq_last_error text: a null handle, `in` or d_peer_offsets; a
+ * null array with a non-zero size; n_peers == 2^32 - 1; the sum of the capacities differs from n_elems or
+ * exceeds 2^32 - 1; a region with pad_ != 0 or src_sel > 1; a region that reaches outside d_offsets
+ * (n_rows > 0), d_peers or its src array (n_rows > 0).
+ * Not covered: `@global` broadcasts (WQ_CLS_BCAST). PeerMap::broadcast_all reaches peers that never
+ * subscribed and hold no id: that is the transport's operation. Heartbeat echoes and record replies are
+ * expressible as unit-row regions with a frame_base behind the received frames; building their frames
+ * into one index space is the caller's. */
+#define WQ_SEND_UNIT_ROWS 0xFFFFFFFFu /* wq_send_region.off_at */
+#define WQ_SEND_NO_SRC    0xFFFFFFFFu /* wq_send_region.src_at */
+typedef struct wq_send_region {   /* HOST array, 32 bytes each */
+    uint32_t off_at;      /* first of n_rows + 1 entries in d_offsets, or WQ_SEND_UNIT_ROWS */
+    uint32_t peers_at;    /* the region's first element in d_peers */
+    uint32_t n_rows;
+    uint32_t capacity;    /* the region's elements in d_peers: what the route call was given */
+    uint32_t src_at;      /* first of n_rows entries in d_src[src_sel], or WQ_SEND_NO_SRC: row r is frame r */
+    uint32_t frame_base;  /* added to the frame index (several frame arrays behind one another in one index space) */
+    uint32_t src_sel;     /* 0 or 1 */
+    uint32_t pad_;        /* 0 */
+} wq_send_region;
+
+typedef struct wq_tick_sends_in {
+    const wq_send_region* regions;           /* HOST, [n_regions] */
+    const uint32_t* d_offsets; size_t n_offsets;
+    const uint32_t* d_peers;   size_t n_pairs;
+    const uint32_t* d_src[2];  size_t n_src[2];   /* l_src and g_src of the dispatch, or NULL */
+    const uint32_t* d_connected;             /* nullable, as wq_peer_major_device */
+    uint32_t n_regions, n_peers, n_frames, pad_;  /* n_frames: size of the frame index space */
+} wq_tick_sends_in;
+
+typedef struct wq_tick_sends_counters {      /* 64 bytes */
+    uint64_t n_regions, n_elems, n_covered, n_kept, n_drop_peer, n_drop_frame;
+    uint32_t error, pad_; uint64_t reserved_;
+} wq_tick_sends_counters;
+
+int wq_tick_sends_device(wq_router* h, const wq_tick_sends_in* in,
+                         uint32_t* d_peer_offsets /* [n_peers + 1] */,
+                         uint32_t* d_frames_out   /* [n_elems] */, size_t n_elems /* sum of capacity */,
+                         wq_tick_sends_counters* d_counters /* nullable */);
+
 /* ---- interest changes: who entered and who left each row between two ticks ----
  * A server that replicates entities (row m of every tick = entity m) sends a spawn to the
  * observers that entered an entity's interest set since the last tick and a despawn to those that

@@ -292,6 +292,34 @@ class FramesRecSrc(ctypes.Structure):  # struct wq_frames_rec_src: device pointe
 assert ctypes.sizeof(FramesRecSrc) == 96
 
 
+# ---- tick sends (wq_tick_sends_device) ----
+SEND_UNIT_ROWS = 0xFFFFFFFF        # WQ_SEND_UNIT_ROWS: wq_send_region.off_at of a region whose row r is element r
+SEND_NO_SRC = 0xFFFFFFFF           # WQ_SEND_NO_SRC: wq_send_region.src_at of a region whose row r is frame r
+SENDS_ERROR_ROWS, SENDS_ERROR_FRAME = 1, 2   # wq_tick_sends_counters.error bits 0 and 1
+# struct wq_send_region: 32 bytes, a HOST array
+SEND_REGION_DTYPE = np.dtype([(k, np.uint32) for k in ("off_at", "peers_at", "n_rows", "capacity", "src_at", "frame_base",
+                                                       "src_sel", "pad_")])
+# struct wq_tick_sends_counters: 64 bytes
+TICK_SENDS_COUNTERS_DTYPE = np.dtype([(k, np.uint64) for k in ("n_regions", "n_elems", "n_covered", "n_kept", "n_drop_peer",
+                                                               "n_drop_frame")] +
+                                     [("error", np.uint32), ("pad_", np.uint32), ("reserved_", np.uint64)])
+
+
+class TickSendsIn(ctypes.Structure):  # struct wq_tick_sends_in: `regions` is a HOST array, the others device pointers
+    _fields_ = [("regions", ctypes.c_void_p), ("d_offsets", ctypes.c_void_p), ("n_offsets", ctypes.c_size_t),
+                ("d_peers", ctypes.c_void_p), ("n_pairs", ctypes.c_size_t), ("d_src", ctypes.c_void_p * 2),
+                ("n_src", ctypes.c_size_t * 2), ("d_connected", ctypes.c_void_p), ("n_regions", ctypes.c_uint32),
+                ("n_peers", ctypes.c_uint32), ("n_frames", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+assert SEND_REGION_DTYPE.itemsize == 32 and TICK_SENDS_COUNTERS_DTYPE.itemsize == 64 and ctypes.sizeof(TickSendsIn) == 96
+
+
+def send_region(off_at=SEND_UNIT_ROWS, peers_at=0, n_rows=0, capacity=0, src_at=SEND_NO_SRC, frame_base=0, src_sel=0, pad_=0):
+    """One wq_send_region as a tuple in SEND_REGION_DTYPE's field order."""
+    return (off_at, peers_at, n_rows, capacity, src_at, frame_base, src_sel, pad_)
+
+
 class ExportFilter(ctypes.Structure):  # struct wq_export_filter; `peers` is a HOST array
     _fields_ = [("world", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("peers", ctypes.c_void_p)]
 

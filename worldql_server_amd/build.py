@@ -18,11 +18,11 @@ BUILD = os.path.join(PKG, "_build")
 LIB = os.path.join(PKG, "libwq_router.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["wq_route.hip", "wq_global.hip", "wq_query.hip", "wq_table.hip", "wq_delta.hip", "wq_shard.hip", "wq_shard_exchange.hip", "wq_sharded.hip", "wq_sharded_slots.hip", "wq_peers.hip", "wq_follow.hip", "wq_csr_diff.hip", "wq_budget.hip", "wq_rotate.hip", "wq_pack.hip", "wq_frames.hip", "wq_decode.hip", "wq_dispatch.hip", "wq_join.hip", "wq_leave.hip", "wq_recdispatch.hip", "wq_slab.hip", "wq_slab_compact.hip", "wq_reply.hip", "wq_records.hip", "wq_table_export.hip", "wq_multi.hip", "wq_router.hip"]
+SOURCES = ["wq_route.hip", "wq_global.hip", "wq_query.hip", "wq_table.hip", "wq_delta.hip", "wq_shard.hip", "wq_shard_exchange.hip", "wq_sharded.hip", "wq_sharded_slots.hip", "wq_peers.hip", "wq_sends.hip", "wq_follow.hip", "wq_csr_diff.hip", "wq_budget.hip", "wq_rotate.hip", "wq_pack.hip", "wq_frames.hip", "wq_decode.hip", "wq_dispatch.hip", "wq_join.hip", "wq_leave.hip", "wq_recdispatch.hip", "wq_slab.hip", "wq_slab_compact.hip", "wq_reply.hip", "wq_records.hip", "wq_table_export.hip", "wq_multi.hip", "wq_router.hip"]
 HOST_SOURCES = ["wq_codec.cpp"]
 CXX = os.environ.get("CXX", "g++")
 HOST_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-pthread", "-Wall"]
-HEADERS = ["lane_xchg.hpp", "wq_device.hpp", "wq_internal.hpp", "route_common.hpp", "route_count.hpp", "route_scan.hpp", "route_emit.hpp", "route_tick.hpp", "route_radius.hpp", "route_spill.hpp", "route_gather.hpp", "table_prims.hpp", "send_rows.hpp", "follow_ops.hpp", "csr_diff_ops.hpp", "peer_major_ops.hpp", "budget_ops.hpp", "rotate_ops.hpp", "pack_ops.hpp", "frame_ops.hpp", "decode_ops.hpp", "dispatch_ops.hpp", "join_ops.hpp", "leave_ops.hpp", "recdispatch_ops.hpp", "slab_ops.hpp", "compact_ops.hpp", "reply_ops.hpp", "record_ops.hpp", "export_ops.hpp", "route_async.hpp", "shard_ctx.hpp"]
+HEADERS = ["lane_xchg.hpp", "wq_device.hpp", "wq_internal.hpp", "route_common.hpp", "route_count.hpp", "route_scan.hpp", "route_emit.hpp", "route_tick.hpp", "route_radius.hpp", "route_spill.hpp", "route_gather.hpp", "table_prims.hpp", "send_rows.hpp", "follow_ops.hpp", "csr_diff_ops.hpp", "peer_major_ops.hpp", "sends_ops.hpp", "budget_ops.hpp", "rotate_ops.hpp", "pack_ops.hpp", "frame_ops.hpp", "decode_ops.hpp", "dispatch_ops.hpp", "join_ops.hpp", "leave_ops.hpp", "recdispatch_ops.hpp", "slab_ops.hpp", "compact_ops.hpp", "reply_ops.hpp", "record_ops.hpp", "export_ops.hpp", "route_async.hpp", "shard_ctx.hpp"]
 # No fast-math and no FMA contraction: coord_clamp must reproduce Rust's f64 op sequence.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]

@@ -324,6 +324,13 @@ struct wq_router {
     // record reply builder (wq_reply.hip): per handle the scan state, term, size and two u64 prefixes; per
     // message the first occurrence of each record shape; sizes and the error word are the frame builder's
     wq::DevBuf rp_ws;
+    // tick sends (wq_sends.hip): the regions and their prefixes on the device, the counters, and the pinned
+    // buffer the regions are uploaded from with the event of the latest copy out of it
+    wq::DevBuf snd_tab, snd_ctrl;
+    void* snd_pinned = nullptr;
+    size_t snd_pinned_bytes = 0;
+    hipEvent_t snd_ev = nullptr;
+    bool snd_pending = false;
     wq::RecStore* rec = nullptr;  // wq_records_open: rows, views, dead list and a call's scratch
     wq::ExportWs exp;             // wq_table_export*
 };
@@ -503,6 +510,11 @@ int launch_frames_build_records(wq_router* h, const wq_frames_src* src, const wq
                                 uint8_t* d_frames, size_t capacity_bytes, uint64_t* d_frame_offsets, uint32_t* d_frame_size,
                                 wq_frames_counters* d_counters);
 void reply_release(wq_router* h);
+// wq_sends.hip: the tick sends on device arrays (asynchronous; the regions are checked there) and the
+// release of its scratch, staging buffer and event.
+int launch_tick_sends(wq_router* h, const wq_tick_sends_in* in, uint32_t* d_peer_offsets, uint32_t* d_frames_out,
+                      size_t n_elems, wq_tick_sends_counters* d_counters);
+void sends_release(wq_router* h);
 void ingest_tables(const wq_router* h, DecTables* t);
 bool records_config(const wq_router* h, RecCfg* cfg);
 // wq_records.hip: frees the record store.

@@ -137,6 +137,7 @@ int wq_router_destroy(wq_router* h) {
     slab_release(h);
     slab_compact_release(h);
     reply_release(h);
+    sends_release(h);
     records_release(h);
     export_release(h);
     for (auto* v : {&h->prof.start, &h->prof.stop, &h->prof.mid1, &h->prof.mid2})
@@ -688,6 +689,15 @@ int wq_peer_major_device(wq_router* h, const uint32_t* d_offsets, const uint32_t
     WQ_HIP(h, hipSetDevice(h->device));
     return launch_peer_major(h, d_offsets, d_peers, n_msgs, n_pairs, d_connected, n_peers, d_peer_offsets,
                              d_msgs_out);
+}
+
+int wq_tick_sends_device(wq_router* h, const wq_tick_sends_in* in, uint32_t* d_peer_offsets, uint32_t* d_frames_out,
+                         size_t n_elems, wq_tick_sends_counters* d_counters) {
+    if (!h) return WQ_E_INVALID;
+    if (!in || !d_peer_offsets) return set_error(h, WQ_E_INVALID, "tick_sends: in or d_peer_offsets is null");
+    if (n_elems && !d_frames_out) return set_error(h, WQ_E_INVALID, "tick_sends: a null array with a non-zero size");
+    WQ_HIP(h, hipSetDevice(h->device));
+    return launch_tick_sends(h, in, d_peer_offsets, d_frames_out, n_elems, d_counters);
 }
 
 int wq_peer_budget_device(wq_router* h, const uint32_t* d_peer_offsets, const uint32_t* d_msgs, uint32_t n_peers,

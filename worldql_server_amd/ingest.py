@@ -1050,6 +1050,56 @@ class IngestTick:
             reads.append(read)
         return cnt, runs, reads
 
+    # ---- the sends: one per-peer frame list from all the regions process() left (wq_tick_sends_device) ----
+    def sends(self, reads, offsets, peers, n_peers: int, connected=None, extra=(), n_frames: int | None = None):
+        """Enqueues wq_tick_sends_device on the regions process() left in `offsets` / `peers` (the tensors it was
+        given; `reads` as it returned them): every read run's LocalMessage region maps its rows to frames
+        through the dispatch's l_src, its GlobalMessage region through g_src. extra: further regions
+        (abi.send_region tuples), e.g. unit rows with a frame_base behind the received frames; n_frames: the
+        size of the frame index space, default the tick's frames. connected: a uint32 device tensor of
+        ceil(n_peers / 32) words, or None. Nothing is read back. Returns (peer_offsets, frames_out): int32
+        device tensors of n_peers + 1 entries and of the regions' capacities' sum, views of grow-only buffers;
+        peer p's frames are frames_out[peer_offsets[p] : peer_offsets[p + 1]], ascending: what
+        Router.peer_pack_device takes with the tick's received frames. read_sends() fetches them."""
+        import torch
+        rows = []
+        for read in reads:
+            for key, sel in (("local", 0), ("global", 1)):
+                g = read[key]
+                if g is not None:
+                    lo, hi = g["rows"]
+                    rows.append(abi.send_region(off_at=g["offsets"], peers_at=g["peers"], n_rows=hi - lo, capacity=g["capacity"],
+                                                src_at=lo, src_sel=sel))
+        rows += [tuple(e) for e in extra]
+        reg = np.array(rows, dtype=abi.SEND_REGION_DTYPE) if rows else np.zeros(0, abi.SEND_REGION_DTYPE)
+        n_elems = int(reg["capacity"].astype(np.int64).sum())
+        if not hasattr(self, "sbuf"):
+            self.sbuf = dict(counters=torch.empty(abi.TICK_SENDS_COUNTERS_DTYPE.itemsize, dtype=torch.uint8, device=self.device))
+        for k, need in (("peer_offsets", n_peers + 1), ("frames", n_elems)):   # grow-only; empty, not zeros (see above)
+            if k not in self.sbuf or self.sbuf[k].numel() < need:
+                self.sbuf[k] = torch.empty(max(2 * need, 8), dtype=torch.int32, device=self.device)
+        have = hasattr(self, "dbuf")
+        src = (self.dbuf["l_src"], self.dbuf["g_src"]) if have else (None, None)
+        self.s_n_peers, self.s_n_elems = n_peers, n_elems
+        self.router.tick_sends_device(reg, offsets.data_ptr() if offsets.numel() else None, offsets.numel(),
+                                      peers.data_ptr() if peers.numel() else None, peers.numel(),
+                                      [t.data_ptr() if have else None for t in src], [self.dcap if have else 0] * 2,
+                                      None if connected is None else connected.data_ptr(), n_peers,
+                                      self.n if n_frames is None else n_frames, self.sbuf["peer_offsets"].data_ptr(),
+                                      self.sbuf["frames"].data_ptr() if n_elems else None, n_elems,
+                                      self.sbuf["counters"].data_ptr())
+        return self.sbuf["peer_offsets"][:n_peers + 1], self.sbuf["frames"][:n_elems]
+
+    def read_sends(self) -> dict:
+        """The last sends()'s outputs as numpy arrays shaped like interest.tick_sends_np's: peer_offsets, frames
+        (the kept ones) and counters (synchronizes; for tests)."""
+        import torch
+        torch.cuda.synchronize()
+        c = self.sbuf["counters"].cpu().numpy().view(abi.TICK_SENDS_COUNTERS_DTYPE)[0]
+        po = self.sbuf["peer_offsets"][:self.s_n_peers + 1].cpu().numpy().view(np.uint32)
+        return dict(peer_offsets=po, frames=self.sbuf["frames"][:int(po[-1])].cpu().numpy().view(np.uint32),
+                    counters={k: int(c[k]) for k in abi.TICK_SENDS_COUNTERS_DTYPE.names if not k.endswith("_")})
+
     def read_dispatch(self) -> dict:
         """Every output of the dispatch and the counters as numpy arrays shaped like dispatch_np's
         (synchronizes; for tests and for the host's share of the tick: the side lists)."""

@@ -15,6 +15,8 @@ peer's list the nearest messages whose sizes sum to at most the peer's bytes.
 peer's frames in one contiguous byte run, in list order.
 `peer_rotate_np` is the definition of the fair share (wq_peer_rotate_device, csrc/wq_rotate.hip): the
 budget's output plus, per peer, the cut elements that follow the peer's cursor in cyclic order.
+`tick_sends_np` is the definition of the tick sends (wq_tick_sends_device, csrc/wq_sends.hip): one
+per-peer list of received frames, ascending, from all the CSR regions a tick's read runs left.
 """
 from __future__ import annotations
 
@@ -119,17 +121,104 @@ def peer_major_np(offsets, peers, n_peers: int, connected=None, capacity: int | 
     p = peers[idx]
     keep = p < n_peers
     if connected is not None:
-        words = np.ascontiguousarray(connected, dtype=np.uint32)
-        q = np.where(keep, p, 0).astype(np.int64)
-        if keep.any() and int(q.max()) >> 5 >= len(words):
-            raise ValueError("connected needs ceil(n_peers / 32) words")
-        bit = (words[q >> 5] >> (q & 31).astype(np.uint32)) & np.uint32(1) if len(words) else np.zeros(total, np.uint32)
-        keep &= bit == 1
+        keep &= _connected_bits(p, keep, connected)
     p, rows = p[keep], rows[keep]
     order = np.argsort(p, kind="stable")
     po = np.zeros(n_peers + 1, dtype=np.uint32)
     np.cumsum(np.bincount(p.astype(np.int64), minlength=n_peers)[:n_peers], out=po[1:])
     return po, np.ascontiguousarray(rows[order], dtype=np.uint32)
+
+
+def _connected_bits(p, keep, connected):
+    """Of the peers p (kept so far where `keep`), which have their bit set in the bitmap's u32 words."""
+    words = np.ascontiguousarray(connected, dtype=np.uint32)
+    q = np.where(keep, p, 0).astype(np.int64)
+    if keep.any() and int(q.max()) >> 5 >= len(words):
+        raise ValueError("connected needs ceil(n_peers / 32) words")
+    if not len(words):
+        return np.zeros(len(p), bool)
+    return ((words[q >> 5] >> (q & 31).astype(np.uint32)) & np.uint32(1)) == 1
+
+
+def tick_sends_check(regions, n_offsets: int, n_pairs: int, n_src, n_peers: int, n_elems: int | None = None) -> int:
+    """The checks wq_tick_sends_device refuses a call by (WQ_E_INVALID), as ValueError; returns the sum
+    of the capacities."""
+    if int(n_peers) >= 0xFFFFFFFF or int(n_peers) < 0:
+        raise ValueError("n_peers must be < 2^32 - 1")
+    total = 0
+    for g in regions:
+        n_rows, cap = int(g["n_rows"]), int(g["capacity"])
+        if int(g["pad_"]) or int(g["src_sel"]) > 1:
+            raise ValueError("a region with pad_ != 0 or src_sel > 1")
+        if n_rows and int(g["off_at"]) != abi.SEND_UNIT_ROWS and int(g["off_at"]) + n_rows + 1 > n_offsets:
+            raise ValueError("a region reaches outside the offsets")
+        if int(g["peers_at"]) + cap > n_pairs:
+            raise ValueError("a region reaches outside the peers")
+        if n_rows and int(g["src_at"]) != abi.SEND_NO_SRC and int(g["src_at"]) + n_rows > n_src[int(g["src_sel"])]:
+            raise ValueError("a region reaches outside its src array")
+        total += cap
+        if total > 0xFFFFFFFF:
+            raise ValueError("the capacities sum to more than 2^32 - 1")
+    if n_elems is not None and int(n_elems) != total:
+        raise ValueError("n_elems is not the sum of the regions' capacities")
+    return total
+
+
+def tick_sends_np(regions, offsets, peers, srcs, n_peers: int, n_frames: int, connected=None, n_elems: int | None = None):
+    """One per-peer frame list from all of a tick's regions: (peer_offsets[n_peers + 1], frames,
+    counters) — the definition of what wq_tick_sends_device writes for ascending offsets.
+
+    regions: abi.SEND_REGION_DTYPE rows. The element space is the regions' [0, capacity) laid end to end.
+    Inside a region the rows are peer_major_np's with capacity = the region's, on its own n_rows + 1
+    offsets from off_at (abi.SEND_UNIT_ROWS: row r is element r, r < min(n_rows, capacity)); the element
+    of row r has the frame frame_base + (srcs[src_sel][src_at + r], or r with abi.SEND_NO_SRC) and the
+    peer peers[peers_at + element]. A covered element is dropped when its frame is >= n_frames
+    (n_drop_frame, error bit 1), else when its peer is >= n_peers or not in `connected` (n_drop_peer). The
+    kept ones are sorted stably by (peer, frame). A row that ends past its region's capacity sets error
+    bit 0. srcs: (l_src, g_src), either may be None. Raises ValueError where the C call returns
+    WQ_E_INVALID, and for offsets that descend (the kernel's result is then unspecified)."""
+    reg = np.ascontiguousarray(regions, dtype=abi.SEND_REGION_DTYPE).reshape(-1)
+    off = np.ascontiguousarray(offsets if offsets is not None else [], dtype=np.uint32).astype(np.int64)
+    peers = np.ascontiguousarray(peers if peers is not None else [], dtype=np.uint32)
+    src = [np.ascontiguousarray(s if s is not None else [], dtype=np.uint32).astype(np.int64) for s in (tuple(srcs or ()) + (None, None))[:2]]
+    n_peers, n_frames = int(n_peers), int(n_frames)
+    total = tick_sends_check(reg, len(off), len(peers), [len(s) for s in src], n_peers, n_elems)
+    error, n_covered = 0, 0
+    ps, fs = [np.zeros(0, np.uint32)], [np.zeros(0, np.int64)]
+    for g in reg:
+        M, cap, base = int(g["n_rows"]), int(g["capacity"]), int(g["frame_base"])
+        if int(g["off_at"]) == abi.SEND_UNIT_ROWS:
+            rows = np.arange(min(M, cap), dtype=np.int64)
+            idx = rows
+        else:
+            o = off[int(g["off_at"]):int(g["off_at"]) + M + 1] if M else np.zeros(1, np.int64)
+            if (np.diff(o) < 0).any():
+                raise ValueError("offsets must ascend (for others the kernel's result is unspecified)")
+            if (o[1:] > cap).any():
+                error |= abi.SENDS_ERROR_ROWS
+            a, b = np.minimum(o[:M], cap), np.minimum(o[1:M + 1], cap)
+            n = b - a
+            rows = np.repeat(np.arange(M, dtype=np.int64), n)
+            idx = np.repeat(a - (np.cumsum(n) - n), n) + np.arange(int(n.sum()), dtype=np.int64)
+        n_covered += len(rows)
+        ps.append(peers[int(g["peers_at"]) + idx])
+        fs.append(base + (rows if int(g["src_at"]) == abi.SEND_NO_SRC else src[int(g["src_sel"])][int(g["src_at"]) + rows]))
+    p, f = np.concatenate(ps), np.concatenate(fs)
+    in_range = f < n_frames
+    if not in_range.all():
+        error |= abi.SENDS_ERROR_FRAME
+    keep = in_range & (p < n_peers)
+    if connected is not None:
+        keep &= _connected_bits(p, keep, connected)
+    n_kept = int(keep.sum())
+    p, f = p[keep], f[keep]
+    order = np.lexsort((f, p))
+    po = np.zeros(n_peers + 1, dtype=np.uint32)
+    np.cumsum(np.bincount(p.astype(np.int64), minlength=n_peers)[:n_peers], out=po[1:])
+    n_drop_frame = int((~in_range).sum())
+    counters = dict(n_regions=len(reg), n_elems=total, n_covered=n_covered, n_kept=n_kept,
+                    n_drop_peer=n_covered - n_kept - n_drop_frame, n_drop_frame=n_drop_frame, error=error)
+    return po, np.ascontiguousarray(f[order], dtype=np.uint32), counters
 
 
 def budget_keys_np(msgs, msg_pos, peer_pos, p: int):

@@ -77,6 +77,7 @@ def load_library(build_if_missing: bool = True):
         "wq_route_global": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)], i32),
         "wq_route_global_device": ([vp, vp, vp, vp, sz, vp, vp, vp, sz, vp], i32),
         "wq_peer_major_device": ([vp, vp, vp, sz, sz, vp, u32, vp, vp], i32),
+        "wq_tick_sends_device": ([vp, ctypes.POINTER(abi.TickSendsIn), vp, vp, sz, vp], i32),
         "wq_peer_budget_device": ([vp, vp, vp, u32, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp], i32),
         "wq_peer_budget_bytes_device": ([vp, vp, vp, u32, sz, vp, vp, sz, vp, sz, ctypes.c_uint64, vp, vp, vp, vp, vp],
                                         i32),
@@ -398,6 +399,24 @@ class Router:
         self._check(self.lib.wq_peer_major_device(self.h, offsets_ptr or None, peers_ptr or None, n_msgs, n_pairs,
                                                   connected_ptr or None, n_peers, peer_offsets_ptr,
                                                   msgs_out_ptr or None))
+
+    def tick_sends_device(self, regions, offsets_ptr: int | None, n_offsets: int, peers_ptr: int | None, n_pairs: int,
+                          src_ptrs, n_src, connected_ptr: int | None, n_peers: int, n_frames: int,
+                          peer_offsets_ptr: int, frames_out_ptr: int | None, n_elems: int,
+                          counters_ptr: int | None = None) -> None:
+        """wq_tick_sends_device: one per-peer list of frames, ascending, from all of a tick's CSR regions;
+        asynchronous on the handle's stream. regions: abi.SEND_REGION_DTYPE rows on the host (free to reuse
+        on return); src_ptrs / n_src: the two src arrays (l_src, g_src) and their lengths; n_elems: the sum
+        of the regions' capacities. The counters (abi.TICK_SENDS_COUNTERS_DTYPE) stay where counters_ptr
+        points. Host definition: interest.tick_sends_np."""
+        reg = np.ascontiguousarray(regions, dtype=abi.SEND_REGION_DTYPE).reshape(-1)
+        src = abi.TickSendsIn(regions=_p(reg) if len(reg) else None, d_offsets=offsets_ptr or None, n_offsets=n_offsets,
+                              d_peers=peers_ptr or None, n_pairs=n_pairs,
+                              d_src=(ctypes.c_void_p * 2)(src_ptrs[0] or None, src_ptrs[1] or None),
+                              n_src=(ctypes.c_size_t * 2)(n_src[0], n_src[1]), d_connected=connected_ptr or None,
+                              n_regions=len(reg), n_peers=n_peers, n_frames=n_frames)
+        self._check(self.lib.wq_tick_sends_device(self.h, ctypes.byref(src), peer_offsets_ptr or None,
+                                                  frames_out_ptr or None, n_elems, counters_ptr or None))
 
     def peer_budget_device(self, peer_offsets_ptr: int | None, msgs_ptr: int | None, n_peers: int, n_in: int,
                            msg_pos_ptr: int | None, n_msgs: int, peer_pos_ptr: int | None, n_peer_pos: int, k: int,
